@@ -14,6 +14,10 @@ fresh synthetic data is copied into the graph's static input buffers every
 step.  Synthetic events are generated and splatted ON DEVICE with the
 native splat kernels.  --no-graphs falls back to eager.
 
+A plain run sets up, warms up, times --steps steps and prints one JSON
+line; --dump-outputs DIR also writes the last timed step's results as
+DIR/<name>.npy.  Secondary measurements belong behind --full (none today).
+
 Single GPU:   python bench.py --gpus 1 --steps 20 --warmup 5
 Multi-GPU (driver-launched):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -68,6 +72,75 @@ def make_sequence_pool(n_sets, seql, n_windows, batch, seqn, window, lr_res,
     return pools
 
 
+_FINDDB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                           "configs", "miopen_finddb")
+
+
+def seed_miopen_finddb():
+    """Copy the recorded MIOpen find results for the flagship shapes
+    (configs/miopen_finddb/) into the user find-db directory; problems the
+    user's db already holds keep their records.  MIOpen's default find
+    then takes its measured solver choices from the db instead of
+    re-benchmarking every solver (~4 min on an empty db, same
+    ms_per_step).  Shapes or MIOpen versions the records do not cover
+    are tuned by MIOpen as before."""
+    db_dir = os.environ.get("MIOPEN_USER_DB_PATH") or \
+        os.path.join(os.path.expanduser("~"), ".config", "miopen")
+    try:
+        os.makedirs(db_dir, exist_ok=True)
+        for fn in os.listdir(_FINDDB_DIR):
+            if not fn.endswith(".ufdb.txt"):
+                continue
+            dst = os.path.join(db_dir, fn)
+            old = ""
+            if os.path.exists(dst):
+                with open(dst) as f:
+                    old = f.read()
+            have = {ln.split("=", 1)[0] for ln in old.splitlines()}
+            with open(os.path.join(_FINDDB_DIR, fn)) as f:
+                new = [ln for ln in f if ln.split("=", 1)[0] not in have]
+            if new:
+                with open(dst, "a") as f:
+                    if old and not old.endswith("\n"):
+                        f.write("\n")
+                    f.writelines(new)
+    except OSError as e:
+        print(f"[bench] MIOpen find-db not seeded ({e}); MIOpen will tune",
+              flush=True)
+
+
+_DUMP_SAMPLE = 1 << 18   # elements kept per prediction window
+
+
+def dump_outputs(out_dir, last, weights, flat_grad):
+    """Write what the last timed step produced as float32 DIR/<name>.npy:
+    its loss, the flat gradient, the weights after its Adam update and the
+    per-window predictions (a fixed seeded sample of _DUMP_SAMPLE elements
+    per window when a window is larger, so the files stay ~20 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    loss, preds = last
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.detach().float().cpu().numpy())
+
+    save("loss", loss.reshape(1))
+    save("grads", flat_grad)
+    save("weights", torch.cat([w.detach().float().reshape(-1)
+                               for w in weights]))
+    n = preds[0].numel()
+    if n > _DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(n, (_DUMP_SAMPLE,), generator=g) \
+            .to(preds[0].device)
+        rows = [prd.reshape(-1)[idx] for prd in preds]
+    else:
+        rows = [prd.reshape(-1) for prd in preds]
+    save("preds", torch.stack(rows))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -98,6 +171,15 @@ def main():
                    default="autocast",
                    help="bf16 via autocast, or pure bf16 weights with an "
                         "fp32 master-weight Adam (no per-op casts)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write the last step's loss, "
+                        "gradients, updated weights and (sampled) "
+                        "predictions to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements; the benchmark "
+                        "has none of its own (config arms and per-kernel "
+                        "figures live in tools/ and scripts/), so today "
+                        "this equals a plain run")
     args = p.parse_args()
 
     assert torch.cuda.is_available(), "bench.py requires an MI355X GPU"
@@ -115,6 +197,7 @@ def main():
                               f"/tmp/miopen-rank{local_rank}")
         torch.cuda.set_device(local_rank)
         dist.init_process_group("nccl", init_method="env://")
+    seed_miopen_finddb()
     device = torch.device(f"cuda:{local_rank}")
     torch.manual_seed(1234 + rank)
 
@@ -176,6 +259,11 @@ def main():
     static_frames = [pools[0][0]]
     static_gts = [list(pools[0][1])]
 
+    # (loss, preds) of the most recent step, for --dump-outputs; a graph
+    # replay rewrites the tensors recorded at capture (graph_outs)
+    last_out = [None]
+    graph_outs = []
+
     import contextlib
 
     def autocast():
@@ -200,6 +288,7 @@ def main():
         for pred, gt in zip(preds, static_gts[0]):
             loss = loss + F.mse_loss(pred.float(), gt)
         loss.backward()
+        last_out[0] = (loss, preds)
         return loss
 
     def comm():
@@ -245,6 +334,7 @@ def main():
 
     def _capture(body):
         graphs = []
+        graph_outs.clear()
         pool_handle = None
         for i in range(len(pools)):
             set_data(i)
@@ -253,6 +343,7 @@ def main():
                 body()
             pool_handle = g.pool()
             graphs.append(g)
+            graph_outs.append(last_out[0])
         torch.cuda.synchronize()
         return graphs
 
@@ -386,6 +477,12 @@ def main():
                 "parallelism": f"dp{world}",
             },
         }))
+
+    if args.dump_outputs and rank == 0:
+        if graphs is not None:
+            last_out[0] = graph_outs[(args.steps - 1) % len(graphs)]
+        dump_outputs(args.dump_outputs, last_out[0],
+                     masters if pure_bf16 else params, flat_grad)
 
     if world > 1:
         dist.destroy_process_group()

@@ -246,6 +246,36 @@ class TestBenchPath:
         assert rec["value"] > 0
         assert rec["config"]["hip_graphs"] == "full"
 
+    def test_bench_dump_outputs(self, ext, tmp_path):
+        """--dump-outputs writes the last timed step's arrays (float32,
+        finite, bounded size); --full is accepted; the result line carries
+        ms_per_step and the step count asked for."""
+        import json
+        import subprocess
+        import sys
+        import numpy as np
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--batch", "1", "--lr-size", "32",
+             "--window", "256", "--full", "--dump-outputs", str(tmp_path)],
+            capture_output=True, text=True, timeout=600,
+            cwd=str(__import__("pathlib").Path(__file__).parent.parent))
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines()
+                          if ln.startswith("{")][-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        arrs = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+        assert set(arrs) == {"loss", "grads", "weights", "preds"}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2**20
+        for name, a in arrs.items():
+            assert a.dtype == np.float32, name
+            assert np.isfinite(a).all(), name
+        assert arrs["loss"].shape == (1,) and arrs["loss"][0] > 0
+        assert arrs["grads"].shape == arrs["weights"].shape
+        assert np.abs(arrs["grads"]).max() > 0
+        # 6 BPTT windows of [1, 2, 64, 64] predictions, unsampled
+        assert arrs["preds"].shape == (6, 2 * 64 * 64)
+
     def test_redistribute_on_gpu(self, ext):
         from esr_amd.ops import redistribute_stack, events_to_stack_no_polarity
         g = torch.Generator().manual_seed(0)

@@ -38,6 +38,34 @@ def test_baseline_config_arms_spec():
     assert "fp16" in f5 and "180" in f5 and "240" in f5
 
 
+def test_bench_seeds_miopen_finddb(tmp_path, monkeypatch):
+    """bench.py merges the recorded find results into the user find-db:
+    missing problems are added, the user's own records win, and a second
+    call changes nothing."""
+    sys.path.insert(0, str(REPO))
+    import bench
+    recorded = sorted(Path(bench._FINDDB_DIR).glob("*.ufdb.txt"))
+    assert recorded, "configs/miopen_finddb holds no find-db"
+    src = recorded[0]
+    lines = src.read_text().splitlines()
+    assert len(lines) > 10 and all("=" in ln for ln in lines)
+
+    db = tmp_path / "db"
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", str(db))
+    bench.seed_miopen_finddb()
+    assert (db / src.name).read_text() == src.read_text()
+
+    # user's own record for the first problem, no trailing newline
+    key = lines[0].split("=", 1)[0]
+    (db / src.name).write_text(key + "=Mine:1,0,algo")
+    bench.seed_miopen_finddb()
+    got = (db / src.name).read_text().splitlines()
+    assert got[0] == key + "=Mine:1,0,algo"
+    assert sorted(got[1:]) == sorted(lines[1:])
+    bench.seed_miopen_finddb()
+    assert (db / src.name).read_text().splitlines() == got
+
+
 def test_txt_to_evs_cli(tmp_path):
     import numpy as np
     rng = np.random.default_rng(0)
