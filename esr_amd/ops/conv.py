@@ -1,4 +1,4 @@
-"""Native bf16 NCHW convolution dispatch (hand-written gfx950 kernels).
+"""Native bf16/fp16 NCHW convolution dispatch (hand-written gfx950 kernels).
 
 Replaces MIOpen + NCHW<->NHWC transposes + autocast casts on the conv
 shapes ESRNet runs (reference ConvLayer ESR:models/submodules.py:159-200,
@@ -32,8 +32,19 @@ ESR_CONV_BWD=native forces all-native, =auto uses native for deep
 stride-1 shapes.  fp32 falls back to torch everywhere (the CPU oracle of
 the parity tests).
 
+fp16 (fp16 autocast, or plain fp16 tensors): the three forward kernels and
+act_grad have an fp16 instantiation (mfma_f32_16x16x32_f16, same tiles and
+LDS layout, fp32 accumulate, one round-to-nearest-even on store; overflow
+saturates to +/-inf like torch's cast).  The native weight-grad and
+input-grad kernels are bf16-only, so the fp16 backward is ALWAYS native
+act_grad + aten.convolution_backward (MIOpen fp16), whatever ESR_CONV_BWD
+says.  The trainer has no GradScaler: fp16 loss scaling is out of scope
+here and the fp16 recipe's numerics are unchanged.
+
 Env: ESR_NATIVE_CONV=0 disables the native path (A/B benching);
-     ESR_CONV_BWD=native routes backward to the native kernels.
+     ESR_CONV_BWD=native routes the bf16 backward to the native kernels;
+     ESR_NATIVE_FP16=0 restores the MIOpen fall-back (and the fp32-island
+     deformable conv) for fp16 only; default on (see _FP16_DEFAULT).
 """
 
 from __future__ import annotations
@@ -50,14 +61,46 @@ __all__ = ["conv2d_act", "native_conv_supported", "ACT_IDS"]
 ACT_IDS = {None: 0, "none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 
 # dispatch telemetry: tests / profiling assert the native path really runs
-stats = {"native_calls": 0}
+# ("native_calls_fp16" counts the fp16 subset, in addition to native_calls)
+stats = {"native_calls": 0, "native_calls_fp16": 0}
 
 _MFMA_MIN_COUT = 32   # below this the MFMA M-tile would idle; use VALU
 _CIK = 32             # K-chunk of the MFMA kernel (pad Cin up to this)
 
 
+# Default of ESR_NATIVE_FP16.  The bf16 dispatch thresholds were measured
+# against MIOpen bf16, so the fp16 default rests on its own measurement:
+# config 5 (4x DVS 180x240, fp16 autocast) end to end, 3 alternating runs,
+# 261.1 frames/s with the path on vs 255.8 on MIOpen (+2.0%; run-to-run
+# range 1.0 / 2.7 frames/s, no overlap) — profiles/README.md, "fp16".
+_FP16_DEFAULT = "1"
+
+
 def _enabled() -> bool:
     return os.environ.get("ESR_NATIVE_CONV", "1") != "0"
+
+
+def native_fp16_enabled() -> bool:
+    return os.environ.get("ESR_NATIVE_FP16", _FP16_DEFAULT) != "0"
+
+
+def compute_dtype(autocast_on: bool, autocast_dtype, x_dtype,
+                  fp16_enabled: bool | None = None):
+    """Dtype half of the dispatch predicate (pure, CPU-testable).
+
+    Takes the autocast state and the input dtype; returns the 16-bit dtype
+    the native kernels should run in, or None for "fall back to torch".
+    Under autocast the autocast dtype decides (operands are cast to it);
+    outside autocast a plain bf16/fp16 tensor is taken as it is.
+    """
+    dt = autocast_dtype if autocast_on else x_dtype
+    if dt == torch.bfloat16:
+        return torch.bfloat16
+    if dt == torch.float16:
+        if fp16_enabled is None:
+            fp16_enabled = native_fp16_enabled()
+        return torch.float16 if fp16_enabled else None
+    return None
 
 
 def _ceil(v: int, m: int) -> int:
@@ -65,7 +108,8 @@ def _ceil(v: int, m: int) -> int:
 
 
 def _pack(w: torch.Tensor) -> torch.Tensor:
-    """[O, I, k, k] -> [k*k, O_p, I_p] bf16, O_p = ceil16(O), I_p = ceil32(I).
+    """[O, I, k, k] -> [k*k, O_p, I_p], O_p = ceil16(O), I_p = ceil32(I);
+    keeps w's dtype (bf16 or fp16).
 
     Matches the A-fragment addressing of conv2d_fwd_mfma_kernel: row = cout,
     contiguous 8-channel groups along ci.
@@ -123,6 +167,9 @@ class _NativeConv2dFn(torch.autograd.Function):
         mode = os.environ.get("ESR_CONV_BWD", "aten")
         native_bwd = mode == "native" or (
             mode == "auto" and stride == 1 and cin >= _MFMA_MIN_COUT)
+        if x.dtype != torch.bfloat16:
+            # wgrad/dgrad kernels are bf16-only: fp16 always takes aten
+            native_bwd = False
         if not native_bwd:
             dx, dw, db = torch.ops.aten.convolution_backward(
                 dpre, x, w, [cout] if ctx.has_bias else None,
@@ -154,13 +201,30 @@ class _NativeConv2dFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
-def shape_supported(conv: torch.nn.Conv2d) -> bool:
-    """Shape half of the dispatch predicate (CPU-testable)."""
+def shape_supported(conv: torch.nn.Conv2d, dtype=None) -> bool:
+    """Shape half of the dispatch predicate (CPU-testable).
+
+    `dtype` is the compute dtype; None or bf16 gives the bf16 table, fp16
+    may route further classes back to MIOpen (measured against MIOpen fp16).
+    """
     if conv.out_channels < _MFMA_MIN_COUT and conv.in_channels < _MFMA_MIN_COUT:
         # tiny-channel class: the v2 register-strip kernel beats MIOpen at
         # stride 1 (head 2.7x, tail 1.3x); the stride-2 enc1 shape still
         # loses (0.67x) and stays on MIOpen (tools/bench_conv.py --valu2)
         if conv.stride[0] != 1:
+            return False
+    if dtype == torch.float16:
+        # fp16 only — measured against MIOpen fp16, which is faster than
+        # MIOpen bf16 on these classes (tools/bench_conv.py --dtype fp16,
+        # two runs, run-to-run spread ~3%; profiles/README.md "fp16"):
+        if conv.out_channels < _MFMA_MIN_COUT <= conv.in_channels:
+            # v1 direct VALU class: attention map 64->1 3x3 0.79-0.80x
+            # (the 1x1 64->2 member of the class: not measured)
+            return False
+        if conv.out_channels >= 128 and conv.kernel_size == (3, 3) \
+                and conv.stride == (1, 1):
+            # wide 3x3 stride-1: gru ur 128->128 0.73-0.75x, resblock
+            # 192->192 0.87-0.88x, recon1 64->128 0.86-0.88x
             return False
     if conv.groups != 1 or conv.dilation != (1, 1):
         return False
@@ -177,28 +241,33 @@ def shape_supported(conv: torch.nn.Conv2d) -> bool:
     return True
 
 
-def native_conv_supported(x: torch.Tensor, conv: torch.nn.Conv2d) -> bool:
+def native_conv_supported(x: torch.Tensor, conv: torch.nn.Conv2d,
+                          dtype=None) -> bool:
     if not (_enabled() and x.is_cuda and get_ext() is not None):
         return False
-    return shape_supported(conv)
+    return shape_supported(conv, dtype)
 
 
 def conv2d_act(x: torch.Tensor, conv: torch.nn.Conv2d, act: str | None):
     """Fused conv+bias+act.  Returns the native-kernel result when the shape
     and dtype qualify, else None (caller falls back to torch)."""
-    if act not in ACT_IDS or not native_conv_supported(x, conv):
+    if act not in ACT_IDS or not (x.is_cuda and _enabled()):
         return None
-    if torch.is_autocast_enabled():
-        if torch.get_autocast_dtype("cuda") != torch.bfloat16:
-            return None   # fp16 autocast: kernels are bf16-native; fall back
-        x = x.to(torch.bfloat16)
-    if x.dtype != torch.bfloat16:
+    autocast_on = torch.is_autocast_enabled()
+    dt = compute_dtype(
+        autocast_on,
+        torch.get_autocast_dtype("cuda") if autocast_on else None, x.dtype)
+    if dt is None or not native_conv_supported(x, conv, dt):
         return None
+    if x.dtype != dt:
+        x = x.to(dt)
     w, b = conv.weight, conv.bias
-    if w.dtype != torch.bfloat16:
-        w = w.to(torch.bfloat16)          # autograd records the cast:
+    if w.dtype != dt:
+        w = w.to(dt)                       # autograd records the cast:
         if b is not None:                  # grads flow back to fp32 masters
-            b = b.to(torch.bfloat16)
+            b = b.to(dt)
     stats["native_calls"] += 1
+    if dt == torch.float16:
+        stats["native_calls_fp16"] += 1
     return _NativeConv2dFn.apply(x.contiguous(), w, b, conv.stride[0],
                                  ACT_IDS[act])

@@ -63,7 +63,7 @@ class _GatesOut(torch.autograd.Function):
         return do_pre, du, dh
 
 
-_FUSED_DTYPES = (torch.float32, torch.bfloat16)
+_FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def gru_gates_ur(ur_pre: torch.Tensor, h: torch.Tensor):

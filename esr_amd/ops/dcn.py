@@ -12,7 +12,10 @@ ESR:models/DCNv2/src/cuda/dcn_v2_cuda.cu:20-216).  Here:
     deformable im2col on gfx950 and a hipBLASLt GEMM through at::bmm, with a
     custom backward (col2im scatter + coordinate gradients).  Unlike the
     reference, the backward is batched — the reference loops per sample
-    (ESR:models/DCNv2/src/cuda/dcn_v2_cuda.cu:150).
+    (ESR:models/DCNv2/src/cuda/dcn_v2_cuda.cu:150).  fp32, bf16 and fp16
+    run natively (16-bit loads, fp32 compute); ESR_NATIVE_FP16=0 sends
+    fp16 through fp32 islands instead.  The opt-in fused MFMA forward
+    (ESR_DCN_FUSED=1) is fp32-only.
 
 Layout conventions (identical to the reference kernels):
   offset: [B, dg*2*kh*kw, Ho, Wo] — per deformable group, per kernel index k
@@ -27,6 +30,7 @@ import math
 import torch
 import torch.nn as nn
 
+from .conv import native_fp16_enabled
 from .native import get_ext
 
 __all__ = ["modulated_deform_conv2d", "DeformAlign2d"]
@@ -145,18 +149,20 @@ def modulated_deform_conv2d(input, offset, mask, weight, bias=None,
             raise RuntimeError(
                 "esr_amd native extension not built - GPU deformable conv "
                 "requires the HIP kernels (run __graft_entry__.build())")
-        if input.dtype == torch.bfloat16:
-            # bf16-native path: the HIP kernels load bf16 and compute fp32
-            # (atomic input-grad accumulates fp32, cast back at the end) —
-            # halves the column-buffer/backward HBM traffic vs the r1
-            # fp32-island design.
-            w16 = weight.to(torch.bfloat16)
-            b16 = None if bias is None else bias.to(torch.bfloat16)
+        if input.dtype == torch.bfloat16 or (
+                input.dtype == torch.float16 and native_fp16_enabled()):
+            # 16-bit-native path: the HIP kernels load bf16/fp16 and compute
+            # fp32 (atomic input-grad accumulates fp32, cast back at the
+            # end) — halves the column-buffer/backward HBM traffic vs the
+            # r1 fp32-island design.
+            dt = input.dtype
+            w16 = weight.to(dt)
+            b16 = None if bias is None else bias.to(dt)
             return _DeformConvHIP.apply(
-                input, offset.to(torch.bfloat16), mask.to(torch.bfloat16),
+                input, offset.to(dt), mask.to(dt),
                 w16, b16, stride, padding, dilation, deformable_groups)
         if input.dtype == torch.float16:
-            # fp16 arrives only via autocast; compute in fp32 islands
+            # ESR_NATIVE_FP16=0: the older fp32-island route
             out = _DeformConvHIP.apply(
                 input.float(), offset.float(), mask.float(), weight.float(),
                 None if bias is None else bias.float(),

@@ -71,17 +71,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("splat_count", &splat_count);
   m.def("splat_stack", &splat_stack);
   m.def("conv2d_fwd_mfma", &conv2d_fwd_mfma,
-        "bf16 NCHW conv fwd, MFMA implicit GEMM, fused bias+act (gfx950)");
+        "bf16/fp16 NCHW conv fwd, MFMA implicit GEMM, fused bias+act (gfx950)");
   m.def("conv2d_fwd_valu", &conv2d_fwd_valu,
-        "bf16 NCHW conv fwd, direct VALU, fused bias+act (gfx950)");
+        "bf16/fp16 NCHW conv fwd, direct VALU, fused bias+act (gfx950)");
   m.def("conv2d_fwd_valu2", &conv2d_fwd_valu2,
-        "bf16 NCHW conv fwd, register-strip VALU v2 for tiny channels");
+        "bf16/fp16 NCHW conv fwd, register-strip VALU v2 for tiny channels");
   m.def("conv2d_dgrad_s2", &conv2d_dgrad_s2,
         "bf16 stride-2 conv input-grad (gfx950)");
   m.def("conv2d_wgrad_mfma", &conv2d_wgrad_mfma,
         "bf16 conv weight-grad, MFMA split-K + fp32 atomics (gfx950)");
-  m.def("act_grad", &act_grad, "fused activation backward (bf16)");
-  m.def("gemm16_probe", &gemm16_probe, "16x16x32 bf16 MFMA fragment probe");
+  m.def("act_grad", &act_grad, "fused activation backward (bf16/fp16)");
+  m.def("gemm16_probe", &gemm16_probe, "16x16x32 bf16/fp16 MFMA fragment probe");
   m.def("redistribute_stack_hip", &redistribute_stack_hip,
         "count stack -> sorted event cloud, device-only "
         "(scan + scatter + segmented radix sort)");

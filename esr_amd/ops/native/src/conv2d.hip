@@ -1,13 +1,20 @@
-// Hand-written gfx950 (CDNA4) direct convolution kernels, bf16 NCHW.
+// Hand-written gfx950 (CDNA4) direct convolution kernels, bf16/fp16 NCHW.
 //
 // Replaces the MIOpen conv + NCHW<->NHWC batched_transpose + autocast cast
 // chain for the shapes ESRNet actually runs (3x3 s1/s2 p1 and 1x1 convs at
 // C in {2..192}, reference ConvLayer ESR:models/submodules.py:159-200 and
-// ConvGRU convs :474-514): bf16-native in/out, fp32 accumulate, fused
+// ConvGRU convs :474-514): 16-bit-native in/out, fp32 accumulate, fused
 // bias + ReLU/sigmoid/tanh epilogues, no layout round trips.
 //
+// Element types: the forward kernels, act_grad and the fragment probe are
+// templated on a small trait (ElemBf16 / ElemFp16: 16-bit load -> float,
+// float -> 16-bit store, MFMA builtin).  Storage is raw 16-bit either way,
+// so tiles, LDS layout and vector stores are shared; the host wrappers
+// dispatch on x.scalar_type() and reject mixed bf16/fp16 operands.  The
+// backward-only kernels (dgrad_s2, wgrad) are bf16-only and say so.
+//
 // Two forward paths, picked by the host by shape:
-//   * MFMA implicit GEMM (mfma_f32_16x16x32_bf16): M = Cout tile (32/64),
+//   * MFMA implicit GEMM (mfma_f32_16x16x32_bf16 / _f16): M = Cout tile (32/64),
 //     N = 64 output pixels (2 rows x 32 cols), K = Cin in chunks of 32,
 //     3x3 taps looped outside K.  The input patch is staged in LDS in a
 //     pixel-major / channel-contiguous layout (40-short slots = 80 B so
@@ -57,18 +64,48 @@ ESR_INLINE ushort f_to_bf16u(float f) {
   return (ushort)(x >> 16);
 }
 
+// Element traits: storage is raw 16-bit (ushort) for both types, so the LDS
+// slot layout, staging loops and vector stores are shared; only the
+// load/store conversions and the MFMA builtin differ.  The C/D fragment
+// layout of mfma_f32_16x16x32 is dtype-independent (guide §3).
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+
+struct ElemBf16 {
+  static ESR_INLINE float to_f(ushort u) { return bf16u_to_f(u); }
+  static ESR_INLINE ushort from_f(float f) { return f_to_bf16u(f); }
+  static ESR_INLINE f32x4 mfma(s16x8 a, s16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+};
+
+struct ElemFp16 {
+  static ESR_INLINE float to_f(ushort u) {
+    return (float)__builtin_bit_cast(_Float16, u);
+  }
+  static ESR_INLINE ushort from_f(float f) {
+    // v_cvt_f16_f32: round-to-nearest-even, overflow -> +/-inf, subnormals
+    // kept — the same result as torch's float->half cast
+    return __builtin_bit_cast(ushort, (_Float16)f);
+  }
+  static ESR_INLINE f32x4 mfma(s16x8 a, s16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(
+        __builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c,
+        0, 0, 0);
+  }
+};
+
 // ---------------------------------------------------------------------------
 // MFMA forward: one block = [32*MREP cout] x [64 pixels] for one frame.
 // Wave grid 2(M) x 2(N); per wave MREP m-frags x 2 n-frags of 16x16.
 // ---------------------------------------------------------------------------
 
-template <int KS, int STRIDE, int ACT, int MREP>
+template <typename E, int KS, int STRIDE, int ACT, int MREP>
 __global__ __launch_bounds__(256)
 void conv2d_fwd_mfma_kernel(
-    const ushort* __restrict__ x,      // [B, Cin, H, W] bf16
-    const ushort* __restrict__ wp,     // [KS*KS, Cout_p, Cin_p] bf16 packed
+    const ushort* __restrict__ x,      // [B, Cin, H, W] bf16/fp16
+    const ushort* __restrict__ wp,     // [KS*KS, Cout_p, Cin_p] packed, same
     const float* __restrict__ bias,    // [Cout] fp32 or nullptr
-    ushort* __restrict__ y,            // [B, Cout, Ho, Wo] bf16
+    ushort* __restrict__ y,            // [B, Cout, Ho, Wo] same as x
     int Cin, int H, int W, int Cout, int Ho, int Wo,
     int Cin_p, int Cout_p, int ntx) {
   constexpr int PH = STRIDE * TH + (KS - 1);
@@ -142,13 +179,12 @@ void conv2d_fwd_mfma_kernel(
             &patch[(py * PW + px) * SLOT + kgrp]);
 #pragma unroll
         for (int m = 0; m < MREP; ++m)
-          acc[m][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[m], bfrag, acc[m][nf], 0, 0, 0);
+          acc[m][nf] = E::mfma(a[m], bfrag, acc[m][nf]);
       }
     }
   }
 
-  // ---- epilogue: bias + activation fused, bf16 stores
+  // ---- epilogue: bias + activation fused, 16-bit stores
   // D layout (guide §3): col = lane&15 (pixel), row = (lane>>4)*4 + j (cout)
 #pragma unroll
   for (int m = 0; m < MREP; ++m) {
@@ -164,7 +200,7 @@ void conv2d_fwd_mfma_kernel(
         float v = acc[m][nf][j];
         if (bias) v += bias[co];
         v = apply_act<ACT>(v);
-        y[(((long long)b * Cout + co) * Ho + oy) * Wo + ox] = f_to_bf16u(v);
+        y[(((long long)b * Cout + co) * Ho + oy) * Wo + ox] = E::from_f(v);
       }
     }
   }
@@ -176,10 +212,10 @@ void conv2d_fwd_mfma_kernel(
 // read neighbouring ix -> coalesced; weights broadcast through K$/L1.
 // ---------------------------------------------------------------------------
 
-template <int KS, int STRIDE, int ACT>
+template <typename E, int KS, int STRIDE, int ACT>
 __global__ void conv2d_fwd_valu_kernel(
     long long n, const ushort* __restrict__ x,
-    const ushort* __restrict__ w,      // [Cout, Cin, KS, KS] bf16 (unpacked)
+    const ushort* __restrict__ w,      // [Cout, Cin, KS, KS] (unpacked)
     const float* __restrict__ bias, ushort* __restrict__ y,
     int Cin, int H, int W, int Cout, int Ho, int Wo) {
   constexpr int PAD = KS / 2;
@@ -205,12 +241,12 @@ __global__ void conv2d_fwd_valu_kernel(
         for (int kx = 0; kx < KS; ++kx) {
           const int ix = ix0 + kx;
           if (ix < 0 || ix >= W) continue;
-          acc += bf16u_to_f(xp[(long long)iy * W + ix]) *
-                 bf16u_to_f(wk[ky * KS + kx]);
+          acc += E::to_f(xp[(long long)iy * W + ix]) *
+                 E::to_f(wk[ky * KS + kx]);
         }
       }
     }
-    y[i] = f_to_bf16u(apply_act<ACT>(acc));
+    y[i] = E::from_f(apply_act<ACT>(acc));
   }
 }
 
@@ -223,11 +259,11 @@ __global__ void conv2d_fwd_valu_kernel(
 // per MAC); this one does ~18 loads per 1152 MACs on the head shape.
 // ---------------------------------------------------------------------------
 
-template <int KS, int STRIDE, int ACT, int COCH>
+template <typename E, int KS, int STRIDE, int ACT, int COCH>
 __global__ __launch_bounds__(256)
 void conv2d_fwd_valu2_kernel(
-    const ushort* __restrict__ x,   // [B, Cin, H, W] bf16
-    const ushort* __restrict__ w,   // [Cout, Cin, KS, KS] bf16
+    const ushort* __restrict__ x,   // [B, Cin, H, W] bf16/fp16
+    const ushort* __restrict__ w,   // [Cout, Cin, KS, KS] same
     const float* __restrict__ bias, ushort* __restrict__ y,
     int Cin, int H, int W, int Cout, int Ho, int Wo,
     long long nstrips, int nsx) {
@@ -275,12 +311,12 @@ void conv2d_fwd_valu2_kernel(
           if (interior) {
 #pragma unroll
             for (int e = 0; e < NPX; ++e)
-              seg[e] = bf16u_to_f(row[ix0 + e]);
+              seg[e] = E::to_f(row[ix0 + e]);
           } else {
 #pragma unroll
             for (int e = 0; e < NPX; ++e) {
               const int ix = ix0 + e;
-              seg[e] = (ix >= 0 && ix < W) ? bf16u_to_f(row[ix]) : 0.f;
+              seg[e] = (ix >= 0 && ix < W) ? E::to_f(row[ix]) : 0.f;
             }
           }
         } else {
@@ -293,7 +329,7 @@ void conv2d_fwd_valu2_kernel(
           float wk[KS];
 #pragma unroll
           for (int kx = 0; kx < KS; ++kx)
-            wk[kx] = bf16u_to_f(wrow[c * Cin * KS * KS + kx]);
+            wk[kx] = E::to_f(wrow[c * Cin * KS * KS + kx]);
 #pragma unroll
           for (int j = 0; j < VEC; ++j) {
             float v = acc[c][j];
@@ -306,7 +342,7 @@ void conv2d_fwd_valu2_kernel(
       }
     }
 
-    // ---- epilogue: bias + act, vector bf16 stores per cout row
+    // ---- epilogue: bias + act, vector 16-bit stores per cout row
     const int nvalid = Wo - ox0 < VEC ? Wo - ox0 : VEC;
 #pragma unroll
     for (int c = 0; c < COCH; ++c) {
@@ -317,7 +353,7 @@ void conv2d_fwd_valu2_kernel(
       for (int j = 0; j < VEC; ++j) {
         float v = acc[c][j];
         if (bias) v += bias[co];
-        packed[j] = f_to_bf16u(apply_act<ACT>(v));
+        packed[j] = E::from_f(apply_act<ACT>(v));
       }
       ushort* dst = y + (((long long)b * Cout + co) * Ho + oy) * Wo + ox0;
       // vector store only when the row base is 16B-aligned (Wo % 8 != 0
@@ -707,21 +743,21 @@ __global__ void conv2d_wgrad_reduce_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Activation backward: dpre = dy * act'(y) elementwise, bf16.
+// Activation backward: dpre = dy * act'(y) elementwise, bf16 or fp16.
 // ---------------------------------------------------------------------------
 
-template <int ACT>
+template <typename E, int ACT>
 __global__ void act_grad_kernel(long long n, const ushort* __restrict__ dy,
                                 const ushort* __restrict__ y,
                                 ushort* __restrict__ dpre) {
   ESR_KERNEL_LOOP(i, n) {
-    const float g = bf16u_to_f(dy[i]);
-    const float v = bf16u_to_f(y[i]);
+    const float g = E::to_f(dy[i]);
+    const float v = E::to_f(y[i]);
     float d;
     if (ACT == 1) d = v > 0.f ? g : 0.f;
     else if (ACT == 2) d = g * v * (1.f - v);
     else d = g * (1.f - v * v);  // tanh
-    dpre[i] = f_to_bf16u(d);
+    dpre[i] = E::from_f(d);
   }
 }
 
@@ -730,6 +766,7 @@ __global__ void act_grad_kernel(long long n, const ushort* __restrict__ dy,
 // fragment maps this file assumes (guide §3; asymmetric-B testable).
 // ---------------------------------------------------------------------------
 
+template <typename E>
 __global__ void gemm16_probe_kernel(const ushort* __restrict__ A,
                                     const ushort* __restrict__ B,
                                     float* __restrict__ C) {
@@ -741,7 +778,7 @@ __global__ void gemm16_probe_kernel(const ushort* __restrict__ A,
     b[j] = (short)B[((lane >> 4) * 8 + j) * 16 + (lane & 15)];
   }
   f32x4 acc = {};
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  acc = E::mfma(a, b, acc);
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     C[((lane >> 4) * 4 + j) * 16 + (lane & 15)] = acc[j];
@@ -772,44 +809,81 @@ __global__ void gemm16_probe_kernel(const ushort* __restrict__ A,
     constexpr int kKS = 3, kST = 1; return __VA_ARGS__();                    \
   }()
 
+// element-type dispatch for the forward kernels / act_grad / probe
+#define DISPATCH_ELEM(TYPE, ...)                                        \
+  [&] {                                                                 \
+    if ((TYPE) == at::kHalf) { using elem_t = ElemFp16; return __VA_ARGS__(); } \
+    using elem_t = ElemBf16; return __VA_ARGS__();                      \
+  }()
+
+// backward-only kernels (dgrad_s2, wgrad) are bf16-only: an fp16 tensor
+// must fail here, not have its bits read as bf16
 static void check_bf16_4d(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
-              t.is_contiguous(), name, ": contiguous bf16 CUDA tensor required");
+              t.is_contiguous(), name,
+              ": contiguous bf16 CUDA tensor required (this kernel is "
+              "bf16-only), got ", t.scalar_type());
 }
 
-// x [B,Cin,H,W] bf16, wp [ntap, Cout_p, Cin_p] bf16, bias [Cout] fp32 | none
+static void check_16bit(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+              (t.scalar_type() == at::kBFloat16 ||
+               t.scalar_type() == at::kHalf), name,
+              ": contiguous bf16 or fp16 CUDA tensor required, got ",
+              t.scalar_type());
+}
+
+// all 16-bit operands of one call share one dtype
+static void check_same_dtype(const at::Tensor& a, const at::Tensor& b,
+                             const char* what) {
+  TORCH_CHECK(a.scalar_type() == b.scalar_type(), what,
+              ": operand dtypes differ (", a.scalar_type(), " vs ",
+              b.scalar_type(), "); bf16 and fp16 cannot be mixed in one call");
+}
+
+static const float* bias_ptr_f32(const c10::optional<at::Tensor>& bias,
+                                 const at::Tensor& x) {
+  if (!bias.has_value()) return nullptr;
+  TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->is_contiguous() &&
+              bias->device() == x.device(),
+              "bias: contiguous fp32 tensor on x's device required, got ",
+              bias->scalar_type());
+  return bias->data_ptr<float>();
+}
+
+// x [B,Cin,H,W] bf16|fp16, wp [ntap, Cout_p, Cin_p] same dtype,
+// bias [Cout] fp32 | none; output has x's dtype
 at::Tensor conv2d_fwd_mfma(const at::Tensor& x, const at::Tensor& wp,
                            const c10::optional<at::Tensor>& bias,
                            int64_t Cout, int64_t ks, int64_t stride,
                            int64_t act) {
-  check_bf16_4d(x, "conv2d_fwd_mfma: x");
-  TORCH_CHECK(wp.is_cuda() && wp.scalar_type() == at::kBFloat16 &&
-              wp.is_contiguous() && wp.dim() == 3, "wp: packed bf16 [ntap,Cop,Cip]");
+  check_16bit(x, "conv2d_fwd_mfma: x");
+  check_16bit(wp, "conv2d_fwd_mfma: wp");
+  check_same_dtype(x, wp, "conv2d_fwd_mfma: x / wp");
+  TORCH_CHECK(x.dim() == 4 && wp.dim() == 3,
+              "x [B,Cin,H,W], wp: packed [ntap,Cop,Cip]");
   const int B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
   const int Cout_p = wp.size(1), Cin_p = wp.size(2);
   TORCH_CHECK(wp.size(0) == ks * ks && Cin_p % CIK == 0 && Cout_p % 16 == 0);
   const int Ho = (H + 2 * (int)(ks / 2) - (int)ks) / (int)stride + 1;
   const int Wo = (W + 2 * (int)(ks / 2) - (int)ks) / (int)stride + 1;
   auto y = at::empty({B, Cout, Ho, Wo}, x.options());
-  const float* bias_ptr = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->is_contiguous());
-    bias_ptr = bias->data_ptr<float>();
-  }
+  const float* bias_ptr = bias_ptr_f32(bias, x);
   const int mrep = (Cout > 32 && Cout_p % 32 == 0) ? 2 : 1;
   const int ntx = (Wo + TW - 1) / TW, nty = (Ho + TH - 1) / TH;
   dim3 grid(ntx * nty, B, (Cout_p + 32 * mrep - 1) / (32 * mrep));
   auto stream = at::hip::getCurrentHIPStream();
+  DISPATCH_ELEM(x.scalar_type(), [&] {
   DISPATCH_KS_STRIDE((int)ks, (int)stride, [&] {
     DISPATCH_ACT((int)act, [&] {
       if (mrep == 2)
-        hipLaunchKernelGGL((conv2d_fwd_mfma_kernel<kKS, kST, kAct, 2>),
+        hipLaunchKernelGGL((conv2d_fwd_mfma_kernel<elem_t, kKS, kST, kAct, 2>),
                            grid, dim3(256), 0, stream,
                            (const ushort*)x.data_ptr(), (const ushort*)wp.data_ptr(),
                            bias_ptr, (ushort*)y.data_ptr(),
                            Cin, H, W, (int)Cout, Ho, Wo, Cin_p, Cout_p, ntx);
       else
-        hipLaunchKernelGGL((conv2d_fwd_mfma_kernel<kKS, kST, kAct, 1>),
+        hipLaunchKernelGGL((conv2d_fwd_mfma_kernel<elem_t, kKS, kST, kAct, 1>),
                            grid, dim3(256), 0, stream,
                            (const ushort*)x.data_ptr(), (const ushort*)wp.data_ptr(),
                            bias_ptr, (ushort*)y.data_ptr(),
@@ -818,34 +892,40 @@ at::Tensor conv2d_fwd_mfma(const at::Tensor& x, const at::Tensor& wp,
     });
     return 0;
   });
+  return 0;
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return y;
 }
 
-// x [B,Cin,H,W] bf16, w [Cout,Cin,ks,ks] bf16 (unpacked), bias fp32 | none
+// x [B,Cin,H,W] bf16|fp16, w [Cout,Cin,ks,ks] same dtype (unpacked),
+// bias fp32 | none
 at::Tensor conv2d_fwd_valu(const at::Tensor& x, const at::Tensor& w,
                            const c10::optional<at::Tensor>& bias,
                            int64_t stride, int64_t act) {
-  check_bf16_4d(x, "conv2d_fwd_valu: x");
-  check_bf16_4d(w, "conv2d_fwd_valu: w");
+  check_16bit(x, "conv2d_fwd_valu: x");
+  check_16bit(w, "conv2d_fwd_valu: w");
+  check_same_dtype(x, w, "conv2d_fwd_valu: x / w");
   const int B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
   const int Cout = w.size(0), ks = w.size(2);
   const int Ho = (H + 2 * (ks / 2) - ks) / (int)stride + 1;
   const int Wo = (W + 2 * (ks / 2) - ks) / (int)stride + 1;
   auto y = at::empty({B, Cout, Ho, Wo}, x.options());
-  const float* bias_ptr = nullptr;
-  if (bias.has_value()) bias_ptr = bias->data_ptr<float>();
+  const float* bias_ptr = bias_ptr_f32(bias, x);
   const long long n = (long long)B * Cout * Ho * Wo;
   auto stream = at::hip::getCurrentHIPStream();
+  DISPATCH_ELEM(x.scalar_type(), [&] {
   DISPATCH_KS_STRIDE(ks, (int)stride, [&] {
     DISPATCH_ACT((int)act, [&] {
-      hipLaunchKernelGGL((conv2d_fwd_valu_kernel<kKS, kST, kAct>),
+      hipLaunchKernelGGL((conv2d_fwd_valu_kernel<elem_t, kKS, kST, kAct>),
                          dim3(esr_grid(n)), dim3(ESR_BLOCK), 0, stream,
                          n, (const ushort*)x.data_ptr(), (const ushort*)w.data_ptr(),
                          bias_ptr, (ushort*)y.data_ptr(), Cin, H, W, Cout, Ho, Wo);
       return 0;
     });
     return 0;
+  });
+  return 0;
   });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return y;
@@ -855,32 +935,33 @@ at::Tensor conv2d_fwd_valu(const at::Tensor& x, const at::Tensor& w,
 at::Tensor conv2d_fwd_valu2(const at::Tensor& x, const at::Tensor& w,
                             const c10::optional<at::Tensor>& bias,
                             int64_t stride, int64_t act) {
-  check_bf16_4d(x, "conv2d_fwd_valu2: x");
-  check_bf16_4d(w, "conv2d_fwd_valu2: w");
+  check_16bit(x, "conv2d_fwd_valu2: x");
+  check_16bit(w, "conv2d_fwd_valu2: w");
+  check_same_dtype(x, w, "conv2d_fwd_valu2: x / w");
   const int B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
   const int Cout = w.size(0), ks = w.size(2);
   TORCH_CHECK(Cin <= 32, "valu2 is for tiny-channel shapes (Cin <= 32)");
   const int Ho = (H + 2 * (ks / 2) - ks) / (int)stride + 1;
   const int Wo = (W + 2 * (ks / 2) - ks) / (int)stride + 1;
   auto y = at::empty({B, Cout, Ho, Wo}, x.options());
-  const float* bias_ptr = nullptr;
-  if (bias.has_value()) bias_ptr = bias->data_ptr<float>();
+  const float* bias_ptr = bias_ptr_f32(bias, x);
   const int coch = Cout >= 8 || Cout > 2 ? 8 : 2;
   const int nsx = (Wo + 7) / 8;
   const long long nstrips = (long long)B * Ho * nsx;
   dim3 grid(esr_grid(nstrips), 1, (Cout + coch - 1) / coch);
   auto stream = at::hip::getCurrentHIPStream();
+  DISPATCH_ELEM(x.scalar_type(), [&] {
   DISPATCH_KS_STRIDE(ks, (int)stride, [&] {
     DISPATCH_ACT((int)act, [&] {
       if (coch == 8)
-        hipLaunchKernelGGL((conv2d_fwd_valu2_kernel<kKS, kST, kAct, 8>),
+        hipLaunchKernelGGL((conv2d_fwd_valu2_kernel<elem_t, kKS, kST, kAct, 8>),
                            grid, dim3(256), 0, stream,
                            (const ushort*)x.data_ptr(),
                            (const ushort*)w.data_ptr(), bias_ptr,
                            (ushort*)y.data_ptr(), Cin, H, W, Cout, Ho, Wo,
                            nstrips, nsx);
       else
-        hipLaunchKernelGGL((conv2d_fwd_valu2_kernel<kKS, kST, kAct, 2>),
+        hipLaunchKernelGGL((conv2d_fwd_valu2_kernel<elem_t, kKS, kST, kAct, 2>),
                            grid, dim3(256), 0, stream,
                            (const ushort*)x.data_ptr(),
                            (const ushort*)w.data_ptr(), bias_ptr,
@@ -889,6 +970,8 @@ at::Tensor conv2d_fwd_valu2(const at::Tensor& x, const at::Tensor& w,
       return 0;
     });
     return 0;
+  });
+  return 0;
   });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return y;
@@ -986,32 +1069,43 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& x, const at::Tensor& dpre,
 }
 
 at::Tensor act_grad(const at::Tensor& dy, const at::Tensor& y, int64_t act) {
-  check_bf16_4d(dy, "act_grad: dy");
+  check_16bit(dy, "act_grad: dy");
+  check_16bit(y, "act_grad: y");
+  check_same_dtype(dy, y, "act_grad: dy / y");
+  TORCH_CHECK(dy.numel() == y.numel(), "act_grad: dy and y sizes differ");
   auto dpre = at::empty_like(dy);
   const long long n = dy.numel();
   auto stream = at::hip::getCurrentHIPStream();
+  DISPATCH_ELEM(dy.scalar_type(), [&] {
   DISPATCH_ACT((int)act, [&] {
     if (kAct == 0) { dpre.copy_(dy); return 0; }
-    hipLaunchKernelGGL((act_grad_kernel<kAct>),
+    hipLaunchKernelGGL((act_grad_kernel<elem_t, kAct>),
                        dim3(esr_grid(n)), dim3(ESR_BLOCK), 0, stream,
                        n, (const ushort*)dy.data_ptr(),
                        (const ushort*)y.data_ptr(), (ushort*)dpre.data_ptr());
     return 0;
+  });
+  return 0;
   });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return dpre;
 }
 
 at::Tensor gemm16_probe(const at::Tensor& A, const at::Tensor& B) {
-  TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kBFloat16 &&
-              A.is_contiguous() && B.is_contiguous() &&
-              A.sizes() == at::IntArrayRef({16, 32}) &&
-              B.sizes() == at::IntArrayRef({32, 16}), "probe: A[16,32] B[32,16] bf16");
+  check_16bit(A, "gemm16_probe: A");
+  check_16bit(B, "gemm16_probe: B");
+  check_same_dtype(A, B, "gemm16_probe: A / B");
+  TORCH_CHECK(A.sizes() == at::IntArrayRef({16, 32}) &&
+              B.sizes() == at::IntArrayRef({32, 16}),
+              "probe: A[16,32] B[32,16]");
   auto C = at::empty({16, 16}, A.options().dtype(at::kFloat));
   auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(gemm16_probe_kernel, dim3(1), dim3(64), 0, stream,
-                     (const ushort*)A.data_ptr(), (const ushort*)B.data_ptr(),
-                     C.data_ptr<float>());
+  DISPATCH_ELEM(A.scalar_type(), [&] {
+    hipLaunchKernelGGL(gemm16_probe_kernel<elem_t>, dim3(1), dim3(64), 0,
+                       stream, (const ushort*)A.data_ptr(),
+                       (const ushort*)B.data_ptr(), C.data_ptr<float>());
+    return 0;
+  });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return C;
 }

@@ -325,15 +325,19 @@ DcnGeom make_geom(const at::Tensor& input, const at::Tensor& weight,
   return g;
 }
 
-// fp32 or bf16 (fp32 compute inside either way)
+// fp32, bf16 or fp16 (fp32 compute inside either way)
 #define DISPATCH_DCN_DTYPE(TEN, ...)                                   \
   [&] {                                                                \
     if ((TEN).scalar_type() == at::kFloat) {                           \
       using scalar_t = float;                                          \
       return __VA_ARGS__();                                            \
     }                                                                  \
+    if ((TEN).scalar_type() == at::kHalf) {                            \
+      using scalar_t = __half;                                         \
+      return __VA_ARGS__();                                            \
+    }                                                                  \
     TORCH_CHECK((TEN).scalar_type() == at::kBFloat16,                  \
-                "deform_conv2d: fp32 or bf16 required");               \
+                "deform_conv2d: fp32, bf16 or fp16 required");         \
     using scalar_t = __hip_bfloat16;                                   \
     return __VA_ARGS__();                                              \
   }()
@@ -356,6 +360,22 @@ at::Tensor dcn_im2col(const at::Tensor& input, const at::Tensor& offset,
   return cols;
 }
 
+bool dcn_dtype_ok(const at::Tensor& t) {
+  return t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16 ||
+         t.scalar_type() == at::kHalf;
+}
+
+// the kernels reinterpret every operand as input's element type
+void dcn_check_same_dtype(const at::Tensor& input, const at::Tensor& offset,
+                          const at::Tensor& mask, const at::Tensor& weight) {
+  TORCH_CHECK(offset.scalar_type() == input.scalar_type() &&
+              mask.scalar_type() == input.scalar_type() &&
+              weight.scalar_type() == input.scalar_type(),
+              "deform_conv2d: input/offset/mask/weight dtypes differ (",
+              input.scalar_type(), ", ", offset.scalar_type(), ", ",
+              mask.scalar_type(), ", ", weight.scalar_type(), ")");
+}
+
 }  // namespace
 
 // deform_conv_fused.hip
@@ -371,9 +391,10 @@ at::Tensor deform_conv2d_forward(
     const at::Tensor& weight, const c10::optional<at::Tensor>& bias,
     int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
     int64_t dg) {
-  TORCH_CHECK(input.is_cuda() && (input.scalar_type() == at::kFloat ||
-                                  input.scalar_type() == at::kBFloat16),
-              "deform_conv2d: fp32/bf16 CUDA tensors required");
+  TORCH_CHECK(input.is_cuda() && dcn_dtype_ok(input),
+              "deform_conv2d: fp32/bf16/fp16 CUDA tensors required, got ",
+              input.scalar_type());
+  dcn_check_same_dtype(input, offset, mask, weight);
   TORCH_CHECK(input.is_contiguous() && offset.is_contiguous() &&
               mask.is_contiguous() && weight.is_contiguous());
   auto g = make_geom(input, weight, sh, sw, ph, pw, dh, dw, dg);
@@ -414,6 +435,13 @@ std::vector<at::Tensor> deform_conv2d_backward(
               mask.is_contiguous() && weight.is_contiguous() &&
               grad_out.is_contiguous(),
               "deform_conv2d_backward: contiguous tensors required");
+  TORCH_CHECK(input.is_cuda() && dcn_dtype_ok(input),
+              "deform_conv2d_backward: fp32/bf16/fp16 CUDA tensors required, "
+              "got ", input.scalar_type());
+  dcn_check_same_dtype(input, offset, mask, weight);
+  TORCH_CHECK(grad_out.scalar_type() == input.scalar_type(),
+              "deform_conv2d_backward: grad_out is ", grad_out.scalar_type(),
+              " but input is ", input.scalar_type());
   auto g = make_geom(input, weight, sh, sw, ph, pw, dh, dw, dg);
   const int K = g.kh * g.kw;
   auto stream = at::hip::getCurrentHIPStream();
@@ -429,7 +457,8 @@ std::vector<at::Tensor> deform_conv2d_backward(
   // dtype-dependent: fp32 measured 3.0x faster TILED (r1 microbench);
   // bf16 measured faster UNTILED (whole-step A/B, +1.8%: the bf16
   // col-grad reads halve the per-contribution kernel's traffic while the
-  // tiled kernel stays LDS-atomic-bound).
+  // tiled kernel stays LDS-atomic-bound).  fp16 has bf16's element size
+  // and takes the same (untiled) default; not measured separately.
   static const int tiled_env = [] {
     const char* e = getenv("ESR_DCN_TILED");
     return e == nullptr ? -1 : (e[0] != '0');

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
 
 #define ESR_INLINE __device__ __forceinline__
 
@@ -28,10 +29,20 @@ template <> ESR_INLINE float esr_to_f32<__hip_bfloat16>(__hip_bfloat16 v) {
   return __bfloat162float(v);
 }
 
+// fp16: exact widening on load
+template <> ESR_INLINE float esr_to_f32<__half>(__half v) {
+  return __half2float(v);
+}
+
 template <typename T> ESR_INLINE T esr_from_f32(float v);
 template <> ESR_INLINE float esr_from_f32<float>(float v) { return v; }
 template <> ESR_INLINE __hip_bfloat16 esr_from_f32<__hip_bfloat16>(float v) {
   return __float2bfloat16(v);
+}
+
+// fp16: round-to-nearest-even, overflow -> +/-inf (torch's float->half cast)
+template <> ESR_INLINE __half esr_from_f32<__half>(float v) {
+  return __float2half_rn(v);
 }
 
 ESR_INLINE float esr_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }

@@ -4,8 +4,8 @@
 // elementwise ops (ESR:models/submodules.py:496-510): 2x sigmoid, tanh,
 // 3 muls, 1 sub, 1 add — each a full HBM round trip.  These kernels fuse
 // the chain into two passes (one before the out-gate conv, one after),
-// each reading its inputs once and writing once.  fp32 and bf16; bf16 is
-// loaded vectorized and computed in fp32 (guide G13).
+// each reading its inputs once and writing once.  fp32, bf16 and fp16; the
+// 16-bit types are loaded as stored and computed in fp32 (guide G13).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -102,6 +102,9 @@ __global__ void gru_out_bwd_kernel(long long n, const T* __restrict__ dh_new,
       return __VA_ARGS__();                                               \
     } else if (TYPE == at::kBFloat16) {                                   \
       using scalar_t = __hip_bfloat16;                                    \
+      return __VA_ARGS__();                                               \
+    } else if (TYPE == at::kHalf) {                                       \
+      using scalar_t = __half;                                            \
       return __VA_ARGS__();                                               \
     } else {                                                              \
       TORCH_CHECK(false, NAME ": unsupported dtype");                     \

@@ -5,7 +5,11 @@ Runs the conv shapes ESRNet's flagship config actually executes (batch
 sizes as in the batch-64 bench step) and prints native vs torch (bf16,
 NCHW) forward and fwd+bwd times.
 
-Usage (GPU box): python tools/bench_conv.py [--iters 50]
+--dtype fp16 runs the same comparison with fp16 operands (native fp16
+kernels vs MIOpen fp16); --wgrad stays bf16 (the native weight-grad kernel
+is bf16-only).
+
+Usage (GPU box): python tools/bench_conv.py [--iters 50] [--dtype fp16]
 """
 
 import argparse
@@ -40,6 +44,9 @@ SHAPES = [
 ]
 
 
+DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
+
+
 def bench(fn, iters, warmup=10):
     for _ in range(warmup):
         fn()
@@ -57,13 +64,13 @@ def valu2_component(args):
     from esr_amd.ops.native import require_ext
     ext = require_ext()
     dev = "cuda:0"
+    dt = DTYPES[args.dtype]
     torch.manual_seed(0)
     tiny = [sh for sh in SHAPES if sh[2] < 32 and sh[3] < 32]
     print(f"{'shape':34s} {'v2 ms':>9s} {'v1 ms':>9s} {'torch':>9s} {'t/v2':>6s}")
     for label, B, cin, cout, h, w, ks, stride, act in tiny:
-        x = torch.randn(B, cin, h, w, device=dev).to(torch.bfloat16)
-        wt = (torch.randn(cout, cin, ks, ks, device=dev) * 0.2) \
-            .to(torch.bfloat16)
+        x = torch.randn(B, cin, h, w, device=dev).to(dt)
+        wt = (torch.randn(cout, cin, ks, ks, device=dev) * 0.2).to(dt)
         b = torch.randn(cout, device=dev).float()
         aid = ACT_IDS[act]
         act_fn = {None: lambda t: t, "relu": F.relu,
@@ -76,7 +83,7 @@ def valu2_component(args):
             return ext.conv2d_fwd_valu(x, wt, b, stride, aid)
 
         def ref():
-            return act_fn(F.conv2d(x, wt, b.to(torch.bfloat16),
+            return act_fn(F.conv2d(x, wt, b.to(dt),
                                    stride=stride, padding=ks // 2))
         # correctness spot check before timing
         got = v2().float()
@@ -97,6 +104,9 @@ def wgrad_component(args):
     ext = require_ext()
     dev = "cuda:0"
     torch.manual_seed(0)
+    if args.dtype != "bf16":
+        print("--wgrad: the native weight-grad kernel is bf16-only; "
+              "timing bf16")
 
     def ceil(v, m):
         return (v + m - 1) // m * m
@@ -131,6 +141,9 @@ def main():
                     help="time the wgrad kernel alone vs aten wgrad-only")
     ap.add_argument("--valu2", action="store_true",
                     help="A/B the tiny-channel strip kernel vs v1 and torch")
+    ap.add_argument("--dtype", choices=sorted(DTYPES), default="bf16",
+                    help="operand dtype of the native kernels and of the "
+                         "MIOpen comparison (--wgrad stays bf16)")
     args = ap.parse_args()
 
     if args.wgrad:
@@ -140,15 +153,15 @@ def main():
 
     from esr_amd.ops.conv import ACT_IDS, _NativeConv2dFn
     dev = "cuda:0"
+    dt = DTYPES[args.dtype]
     torch.manual_seed(0)
 
     total_n, total_t = 0.0, 0.0
     print(f"{'shape':34s} {'native ms':>10s} {'torch ms':>10s} {'x':>6s}")
     for label, B, cin, cout, h, w, ks, stride, act in SHAPES:
-        x = torch.randn(B, cin, h, w, device=dev).to(torch.bfloat16)
-        wt = (torch.randn(cout, cin, ks, ks, device=dev) * 0.2) \
-            .to(torch.bfloat16)
-        b = torch.randn(cout, device=dev).to(torch.bfloat16)
+        x = torch.randn(B, cin, h, w, device=dev).to(dt)
+        wt = (torch.randn(cout, cin, ks, ks, device=dev) * 0.2).to(dt)
+        b = torch.randn(cout, device=dev).to(dt)
         act_fn = {None: lambda t: t, "relu": F.relu,
                   "sigmoid": torch.sigmoid, "tanh": torch.tanh}[act]
 
