@@ -15,7 +15,10 @@ import yaml
 
 OPTIMIZERS = {
     "Adam": "Adam", "AdamW": "AdamW", "SGD": "SGD", "RMSprop": "RMSprop",
+    # esr_amd.optim: flat-buffer HIP Adam with capture-safe loss scaling
+    "FlatAdam": "FlatAdam", "FlatAdamW": "FlatAdamW",
 }
+FLAT_OPTIMIZERS = ("FlatAdam", "FlatAdamW")
 SCHEDULERS = {
     "ExponentialLR": "ExponentialLR", "StepLR": "StepLR",
     "CosineAnnealingLR": "CosineAnnealingLR", "MultiStepLR": "MultiStepLR",
@@ -26,6 +29,9 @@ def build_optimizer(name: str, params, **kwargs):
     import torch.optim as optim
     if name not in OPTIMIZERS:
         raise KeyError(f"unknown optimizer '{name}'; known: {sorted(OPTIMIZERS)}")
+    if name in FLAT_OPTIMIZERS:
+        from .. import optim as flat_optim
+        return getattr(flat_optim, OPTIMIZERS[name])(params, **kwargs)
     return getattr(optim, OPTIMIZERS[name])(params, **kwargs)
 
 

@@ -4,8 +4,8 @@ The on-disk structure is the reference's public checkpoint API
 (ESR:train_ours_cnt_seq.py:642-658): a single torch.save dict
 
     {model: {name, states}, lr_scheduler: {name, states},
-     optimizer: {name, states}, config, trainer: {training_mode,
-     epoch|iteration, monitor_best}}
+     optimizer: {name, states[, grad_scaler]}, config,
+     trainer: {training_mode, epoch|iteration, monitor_best}}
 
 so inference can rebuild the model from the config stored inside the
 checkpoint (ESR:infer_ours_cnt.py:118-132).  Resume verifies component
@@ -20,7 +20,8 @@ __all__ = ["save_checkpoint", "Resumer", "load_model_from_checkpoint"]
 
 
 def save_checkpoint(path, config: dict, model, optimizer=None,
-                    lr_scheduler=None, trainer_state: dict | None = None):
+                    lr_scheduler=None, trainer_state: dict | None = None,
+                    grad_scaler=None):
     model_sd = model.module.state_dict() if hasattr(model, "module") \
         else model.state_dict()
     state = {
@@ -31,6 +32,10 @@ def save_checkpoint(path, config: dict, model, optimizer=None,
                       "states": optimizer.state_dict() if optimizer else {}},
         "config": config,
     }
+    if grad_scaler is not None:
+        # eager loss scaling with a non-Flat optimizer (FlatAdam keeps its
+        # scaler state inside its own state dict)
+        state["optimizer"]["grad_scaler"] = grad_scaler.state_dict()
     if trainer_state is not None:
         state["trainer"] = trainer_state
     torch.save(state, path)
@@ -46,10 +51,15 @@ class Resumer:
         self.logger = logger
         self.config = config or {}
 
+    # FlatAdam/FlatAdamW checkpoint in torch.optim.Adam/AdamW's layout, so
+    # each pair counts as the same component
+    _ALIASES = {"FlatAdam": "Adam", "FlatAdamW": "AdamW"}
+
     def _check(self, section):
         name_ckpt = self.ckpt[section]["name"]
         name_cfg = self.config.get(section, {}).get("name")
-        if name_cfg is not None and name_cfg != name_ckpt:
+        canon = lambda n: self._ALIASES.get(n, n)  # noqa: E731
+        if name_cfg is not None and canon(name_cfg) != canon(name_ckpt):
             raise ValueError(
                 f"checkpoint {section} '{name_ckpt}' != config '{name_cfg}'")
 
@@ -61,10 +71,13 @@ class Resumer:
         target = model.module if hasattr(model, "module") else model
         target.load_state_dict(self.ckpt[section]["states"])
 
-    def resume_optimizer(self, optimizer, section="optimizer"):
+    def resume_optimizer(self, optimizer, section="optimizer",
+                         grad_scaler=None):
         self._check(section)
         if self.ckpt[section]["states"]:
             optimizer.load_state_dict(self.ckpt[section]["states"])
+        if grad_scaler is not None and self.ckpt[section].get("grad_scaler"):
+            grad_scaler.load_state_dict(self.ckpt[section]["grad_scaler"])
 
     def resume_lr_scheduler(self, sched, section="lr_scheduler"):
         self._check(section)

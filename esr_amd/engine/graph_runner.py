@@ -11,6 +11,11 @@ DDP-wrapped — gradients live in one flat buffer that is all-reduced with a
 single RCCL call inside the graph (xGMI collectives on this model's few-MB
 gradients are latency-bound, so one fused call is the right shape —
 SURVEY §2.4).
+
+With FlatAdam/FlatAdamW (esr_amd/optim) the optimizer's own flat gradient is
+the all-reduced buffer, the backward runs on ``optimizer.scale_loss(loss)``
+and the overflow skip / scale update are device-side parts of the captured
+step; the learning rate is a device scalar refreshed before each replay.
 """
 
 from __future__ import annotations
@@ -88,8 +93,11 @@ class GraphedBPTTStep:
                     pred = self.model(inp)
                 mse = F.mse_loss(pred.float(), gt)
                 loss = loss + mse
-        loss.backward()
+        scale_loss = getattr(self.optimizer, "scale_loss", None)
+        (scale_loss(loss) if scale_loss else loss).backward()
         if self.world > 1:
+            # stays before the optimizer: an inf/NaN survives the sum, so
+            # every rank takes the same skip decision
             dist.all_reduce(self.flat_grad)
             self.flat_grad.div_(self.world)
         self.optimizer.step()
@@ -97,15 +105,31 @@ class GraphedBPTTStep:
 
     def _snapshot_state(self):
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
+        # FlatAdam: device scalars (loss scale, growth tracker, step,
+        # skipped count) and the moments, which a resumed run has loaded
+        self._flat_snapshot = None
+        if hasattr(self.optimizer, "device_state"):
+            opt = self.optimizer
+            self._flat_snapshot = [
+                (buf, buf.detach().clone())
+                for buf in (opt.device_state, opt.exp_avg, opt.exp_avg_sq,
+                            opt.max_exp_avg_sq) if buf is not None]
         return [p.detach().clone() for p in params], params
 
     def _restore_state(self, snapshot, params):
         """Undo the warmup steps: params back to their pre-warmup values and
         the optimizer state zeroed in place (= never stepped).  In-place so
-        the state tensors the capture records keep their addresses."""
+        the state tensors the capture records keep their addresses.
+        FlatAdam's moments and device scalars (scale, tracker, step, skipped)
+        go back to their pre-warmup values instead: warm-up steps on garbage
+        data may legitimately overflow and back the scale off."""
         with torch.no_grad():
             for p, s in zip(params, snapshot):
                 p.copy_(s)
+            if self._flat_snapshot is not None:
+                for buf, saved in self._flat_snapshot:
+                    buf.copy_(saved)
+                self._flat_snapshot = None
             for state in self.optimizer.state.values():
                 for v in state.values():
                     if torch.is_tensor(v):
@@ -139,5 +163,9 @@ class GraphedBPTTStep:
                                    window_inputs, window_gts):
             si.copy_(inp, non_blocking=True)
             sg.copy_(gt, non_blocking=True)
+        sync_lr = getattr(self.optimizer, "sync_lr", None)
+        if sync_lr is not None:
+            # lr is a device scalar read by the captured FlatAdam step
+            sync_lr()
         self.graph.replay()
         return self.static_loss, self.static_mse

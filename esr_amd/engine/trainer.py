@@ -11,7 +11,11 @@ MI355X deltas:
   * optional bf16 autocast for forward+loss (the reference is fp32-only);
   * the per-iteration dist.barrier() is dropped (DDP's all-reduce is the
     sync point; the barrier is one more latency-bound xGMI collective);
-  * non_blocking H2D copies from pinned buffers.
+  * non_blocking H2D copies from pinned buffers;
+  * optional dynamic loss scaling (top-level ``loss_scale`` key) for fp16
+    autocast: device-side inside FlatAdam/FlatAdamW (capture-safe, works
+    under hip_graphs), torch.amp.GradScaler for any other optimizer in
+    eager mode.
 """
 
 from __future__ import annotations
@@ -22,17 +26,49 @@ import torch
 import torch.nn.functional as F
 
 from ..config import build_lr_scheduler, build_optimizer
+from ..config.parser import FLAT_OPTIMIZERS
 from ..parallel import get_rank, reduce_tensor
 from ..utils import MetricTracker, MetricWriter
 from .checkpoint import Resumer, save_checkpoint
 
-__all__ = ["Trainer"]
+__all__ = ["Trainer", "loss_scale_plan"]
+
+
+def loss_scale_plan(cfg: dict, use_graphs: bool):
+    """Decide who scales the loss for this config.
+
+    Returns ``(mode, settings)``: ``("off", None)`` when the top-level
+    ``loss_scale`` key is absent or disabled, ``("flat", settings)`` when
+    the optimizer is FlatAdam/FlatAdamW (device-side, capture-safe), and
+    ``("grad_scaler", settings)`` for any other optimizer in eager mode.
+    A non-Flat optimizer under hip_graphs raises: GradScaler's skip decision
+    cannot be recorded into the captured step.
+    """
+    from ..optim.flat_adam import LOSS_SCALE_DEFAULTS
+    ls = cfg.get("loss_scale") or {}
+    if not ls.get("enabled", False):
+        return "off", None
+    settings = {k: v for k, v in ls.items() if k != "enabled"}
+    unknown = set(settings) - set(LOSS_SCALE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown loss_scale keys {sorted(unknown)}; "
+                         f"known: {sorted(LOSS_SCALE_DEFAULTS)}")
+    name = cfg["optimizer"]["name"]
+    if name in FLAT_OPTIMIZERS:
+        return "flat", settings
+    if use_graphs:
+        raise ValueError(
+            f"loss_scale with trainer.hip_graphs needs a capture-safe "
+            f"optimizer: use FlatAdam/FlatAdamW instead of '{name}' "
+            f"(torch.amp.GradScaler's skip decision cannot be captured)")
+    return "grad_scaler", settings
 
 
 class Trainer:
     def __init__(self, config_parser, train_dataloader, valid_dataloader,
                  model, loss_fns, optimizer, lr_scheduler, logger, device,
-                 resume: str | None = None, reset: bool = False):
+                 resume: str | None = None, reset: bool = False,
+                 grad_scaler=None):
         self.config_parser = config_parser
         self.cfg = config_parser.config
         self.train_dataloader = train_dataloader
@@ -43,6 +79,8 @@ class Trainer:
         self.lr_scheduler = lr_scheduler
         self.logger = logger
         self.device = device
+        # torch.amp.GradScaler for the eager non-Flat loss-scaling case
+        self.grad_scaler = grad_scaler
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16,
                           None: None, "fp32": None}[
                               self.cfg.get("precision", None)]
@@ -138,8 +176,12 @@ class Trainer:
         key = (shared, n_windows, inp_shape, gt_shape)
         if self._graph_step is not None and self._graph_step[0] == key:
             return self._graph_step[1]
-        params = [p for p in self.model.parameters() if p.requires_grad]
-        flat = flatten_grads(params, self.device)
+        if hasattr(self.optimizer, "flat_grad"):
+            # FlatAdam already owns the flat gradient the params point into
+            flat = self.optimizer.flat_grad
+        else:
+            params = [p for p in self.model.parameters() if p.requires_grad]
+            flat = flatten_grads(params, self.device)
         runner = GraphedBPTTStep(
             self.model, self.optimizer, flat, n_windows,
             inp_shape, gt_shape, self.device,
@@ -207,9 +249,18 @@ class Trainer:
                     mse_loss = self.loss_fns["mse"](pred.float(), gt.float())
                 loss = loss + mse_loss
         if train:
-            loss.backward()
-            self._sync_grads_if_needed()
-            self.optimizer.step()
+            # the scaled loss only drives the backward; the un-scaled loss
+            # is what gets logged and returned
+            if self.grad_scaler is not None:
+                self.grad_scaler.scale(loss).backward()
+                self._sync_grads_if_needed()
+                self.grad_scaler.step(self.optimizer)
+                self.grad_scaler.update()
+            else:
+                scale_loss = getattr(self.optimizer, "scale_loss", None)
+                (scale_loss(loss) if scale_loss else loss).backward()
+                self._sync_grads_if_needed()
+                self.optimizer.step()
         return loss.detach(), mse_loss.detach(), pred.detach()
 
     def _sync_grads_if_needed(self):
@@ -222,6 +273,14 @@ class Trainer:
         if world <= 1 or hasattr(self.model, "module"):
             return
         import torch.distributed as dist
+        flat_grad = getattr(getattr(self, "optimizer", None), "flat_grad",
+                            None)
+        if flat_grad is not None:
+            # FlatAdam: every .grad is a view of this one buffer; an inf/NaN
+            # survives the sum, so every rank skips the same step
+            dist.all_reduce(flat_grad)
+            flat_grad.div_(world)
+            return
         grads = [p.grad for p in self.model.parameters()
                  if p.requires_grad and p.grad is not None]
         if not grads:
@@ -298,6 +357,7 @@ class Trainer:
                             f"Train epoch {epoch + 1} iter {iter_idx}/"
                             f"{self.iterations} mse {reduced_mse.item():.4e} "
                             f"loss {reduced_loss.item():.4e} lr {lr:.3e}")
+                        self._log_loss_scale()
                     self._maybe_visualize(iter_idx, inputs_seq, pred)
 
                 if self.do_validation and iter_idx % self.valid_step == 0 \
@@ -356,6 +416,7 @@ class Trainer:
                         self.logger.info(
                             f"Train epoch {epoch} [{idx}/{len(self.train_dataloader)}]"
                             f" mse {reduced_mse.item():.4e}")
+                        self._log_loss_scale()
             log = self.train_metrics.result()
             if self.do_validation and epoch % self.valid_step == 0:
                 with torch.no_grad():
@@ -369,6 +430,29 @@ class Trainer:
                 break
         if get_rank() == 0:
             self.logger.info("Training completes!")
+
+    def loss_scale_stats(self):
+        """(loss scale, skipped steps or None) of the active scaler, or None
+        when loss scaling is off.  Reading synchronizes with the device:
+        call at logging cadence only."""
+        if getattr(self.optimizer, "loss_scaling", False):
+            return (self.optimizer.loss_scale_value,
+                    self.optimizer.skipped_steps)
+        if self.grad_scaler is not None:
+            return self.grad_scaler.get_scale(), None
+        return None
+
+    def _log_loss_scale(self):
+        stats = self.loss_scale_stats()
+        if stats is None:
+            return
+        scale, skipped = stats
+        self.writer.add_scalar("loss_scale", scale)
+        msg = f"loss_scale {scale:g}"
+        if skipped is not None:
+            self.writer.add_scalar("skipped_steps", skipped)
+            msg += f" skipped_steps {skipped}"
+        self.logger.info(msg)
 
     def _valid(self, stamp):
         self.model.eval()
@@ -457,12 +541,14 @@ class Trainer:
                          "monitor_best": self.mnt_best}
         fn = self.checkpoint_dir / f"checkpoint-{key}{idx}.pth"
         save_checkpoint(fn, self.cfg, self.model, self.optimizer,
-                        self.lr_scheduler, trainer_state)
+                        self.lr_scheduler, trainer_state,
+                        grad_scaler=self.grad_scaler)
         self.logger.info(f"Saved checkpoint: {fn}")
         if best:
             bfn = self.checkpoint_dir / f"model_best_until_{key}{idx}.pth"
             save_checkpoint(bfn, self.cfg, self.model, self.optimizer,
-                            self.lr_scheduler, trainer_state)
+                            self.lr_scheduler, trainer_state,
+                            grad_scaler=self.grad_scaler)
             self.logger.info(f"Saved current best: {bfn}")
 
     def _resume_checkpoint(self, path, reset):
@@ -476,7 +562,8 @@ class Trainer:
                 self.start_iteration = tstate["iteration"] + 1
             self.mnt_best = tstate["monitor_best"]
         resumer.resume_model(self.model)
-        resumer.resume_optimizer(self.optimizer)
+        resumer.resume_optimizer(self.optimizer,
+                                 grad_scaler=self.grad_scaler)
         resumer.resume_lr_scheduler(self.lr_scheduler)
         if get_rank() == 0:
             self.logger.info(f"Resumed from {path}")
@@ -499,11 +586,20 @@ def build_training(config_parser, device, logger, resume=None, reset=False):
     model = build_model(cfg["model"]["name"], **cfg["model"]["args"]).to(device)
     use_graphs = cfg["trainer"].get("hip_graphs", False) \
         and device.type == "cuda"
+    opt_name = cfg["optimizer"]["name"]
+    flat_opt = opt_name in FLAT_OPTIMIZERS
+    ls_mode, ls_settings = loss_scale_plan(cfg, use_graphs)
     if use_graphs:
         # graphed mode does its own single-bucket RCCL all-reduce inside the
         # captured step; DDP's hook-driven reducer is not used
         if cfg.get("sync_bn", False):
             raise ValueError("hip_graphs is incompatible with sync_bn")
+    elif flat_opt:
+        # FlatAdam re-points p.data/p.grad into its flat buffers, which a
+        # DDP reducer's bucket views would fight over; the un-wrapped model
+        # is synchronized by Trainer._sync_grads_if_needed instead
+        if cfg.get("sync_bn", False):
+            raise ValueError(f"{opt_name} is incompatible with sync_bn")
     else:
         model = wrap_ddp(model, device=device if device.type == "cuda" else None,
                          sync_bn=cfg.get("sync_bn", False))
@@ -511,12 +607,16 @@ def build_training(config_parser, device, logger, resume=None, reset=False):
     loss_fns = {"mse": nn.MSELoss(), "l1": nn.L1Loss()}
     params = [p for p in model.parameters() if p.requires_grad]
     opt_kwargs = dict(cfg["optimizer"]["args"])
-    if use_graphs and cfg["optimizer"]["name"] in ("Adam", "AdamW"):
+    if use_graphs and opt_name in ("Adam", "AdamW"):
         opt_kwargs["capturable"] = True
-    optimizer = build_optimizer(cfg["optimizer"]["name"], params,
-                                **opt_kwargs)
+    if ls_mode == "flat":
+        opt_kwargs["loss_scale"] = ls_settings
+    optimizer = build_optimizer(opt_name, params, **opt_kwargs)
+    grad_scaler = None
+    if ls_mode == "grad_scaler":
+        grad_scaler = torch.amp.GradScaler(device.type, **ls_settings)
     lr_scheduler = build_lr_scheduler(cfg["lr_scheduler"]["name"], optimizer,
                                       **cfg["lr_scheduler"]["args"])
     return Trainer(config_parser, train_loader, valid_loader, model, loss_fns,
                    optimizer, lr_scheduler, logger, device,
-                   resume=resume, reset=reset)
+                   resume=resume, reset=reset, grad_scaler=grad_scaler)

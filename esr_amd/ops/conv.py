@@ -38,8 +38,9 @@ LDS layout, fp32 accumulate, one round-to-nearest-even on store; overflow
 saturates to +/-inf like torch's cast).  The native weight-grad and
 input-grad kernels are bf16-only, so the fp16 backward is ALWAYS native
 act_grad + aten.convolution_backward (MIOpen fp16), whatever ESR_CONV_BWD
-says.  The trainer has no GradScaler: fp16 loss scaling is out of scope
-here and the fp16 recipe's numerics are unchanged.
+says.  Nothing here scales the loss: fp16 gradients below 6e-8 flush to
+zero unless the trainer's opt-in `loss_scale` config key is set (device-side
+in esr_amd/optim FlatAdam, torch.amp.GradScaler otherwise).
 
 Env: ESR_NATIVE_CONV=0 disables the native path (A/B benching);
      ESR_CONV_BWD=native routes the bf16 backward to the native kernels;

@@ -55,6 +55,14 @@ at::Tensor gemm16_probe(const at::Tensor&, const at::Tensor&);
 std::vector<at::Tensor> redistribute_stack_hip(const at::Tensor&, int64_t,
                                                int64_t, int64_t, int64_t);
 
+// flat_adam.hip
+void flat_grad_finite_check(const at::Tensor&, at::Tensor&);
+void flat_adam_step(at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
+                    const c10::optional<at::Tensor>&, const at::Tensor&,
+                    double, double, double, double, bool);
+void flat_scale_update(at::Tensor&, bool, double, double, int64_t, double,
+                       double);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
         "modulated deformable conv forward (gfx950)");
@@ -85,5 +93,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("redistribute_stack_hip", &redistribute_stack_hip,
         "count stack -> sorted event cloud, device-only "
         "(scan + scatter + segmented radix sort)");
+  m.def("flat_grad_finite_check", &flat_grad_finite_check,
+        "raise found_inf in the device state if the flat fp32 grad has "
+        "inf/NaN");
+  m.def("flat_adam_step", &flat_adam_step,
+        "flat-buffer Adam/AdamW step with device-side un-scale and skip");
+  m.def("flat_scale_update", &flat_scale_update,
+        "GradScaler-style scale/step update of the device state");
   m.attr("gfx_arch") = "gfx950";
 }
