@@ -63,6 +63,11 @@ void flat_adam_step(at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
 void flat_scale_update(at::Tensor&, bool, double, double, int64_t, double,
                        double);
 
+// stream_ingest.hip
+void stream_window_advance(at::Tensor&, const at::Tensor&);
+void stream_splat_ragged(const at::Tensor&, const at::Tensor&,
+                         const at::Tensor&, at::Tensor&, int64_t);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
         "modulated deformable conv forward (gfx950)");
@@ -100,5 +105,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flat-buffer Adam/AdamW step with device-side un-scale and skip");
   m.def("flat_scale_update", &flat_scale_update,
         "GradScaler-style scale/step update of the device state");
+  m.def("stream_window_advance", &stream_window_advance,
+        "per-stream sliding-window shift/reset of a [seqn,S,2,kH,kW] buffer, "
+        "control read from a device tensor");
+  m.def("stream_splat_ragged", &stream_splat_ragged,
+        "splat concatenated per-stream LR event windows into the newest "
+        "frame of a [seqn,S,2,kH,kW] buffer");
   m.attr("gfx_arch") = "gfx950";
 }

@@ -166,7 +166,11 @@ void conv2d_fwd_mfma_kernel(
       s16x8 a[MREP];
 #pragma unroll
       for (int m = 0; m < MREP; ++m) {
-        const int row = co0 + wm * 16 * MREP + m * 16 + (lane & 15);
+        // the last cout block may reach past Cout_p (216 -> 224 packed
+        // rows, blocks of 64): clamp, or the load runs off the end of wp;
+        // those rows' results are dropped by the co >= Cout test below
+        int row = co0 + wm * 16 * MREP + m * 16 + (lane & 15);
+        row = row < Cout_p ? row : Cout_p - 1;
         a[m] = *reinterpret_cast<const s16x8*>(
             &wp[((long long)tap * Cout_p + row) * Cin_p + ci0 + kgrp]);
       }
