@@ -66,12 +66,16 @@ class SequenceDataset(Dataset):
         with self._epoch.get_lock():
             self._epoch.value = int(epoch)
 
-    def __getitem__(self, i):
+    def window_plan(self, i):
+        """The item's augmentation seed and its L steps as (window index,
+        paused) pairs: a paused step repeats the frozen index with zero
+        input.  `__getitem__` and the device-resident loader both build
+        item i from this plan."""
         assert 0 <= i < self.length
         seed = _stable_seed(self.seed_base, self._epoch.value, i)
         rng = random.Random(seed ^ 0x5DEECE66D)   # pause chain, same seed
         j = i * self.step_size
-        sequence = [self.dataset.__getitem__(j, seed=seed)]
+        steps = [(j, False)]
         k = 0
         paused = False
         enabled = self.pause_cfg.get("enabled", False)
@@ -81,9 +85,12 @@ class SequenceDataset(Dataset):
                 prob = (self.pause_cfg["proba_pause_when_paused"] if paused
                         else self.pause_cfg["proba_pause_when_running"])
                 paused = u < prob
-            if paused:
-                sequence.append(self.dataset.__getitem__(j + k, pause=True, seed=seed))
-            else:
+            if not paused:
                 k += 1
-                sequence.append(self.dataset.__getitem__(j + k, seed=seed))
-        return sequence
+            steps.append((j + k, paused))
+        return seed, steps
+
+    def __getitem__(self, i):
+        seed, steps = self.window_plan(i)
+        return [self.dataset.__getitem__(idx, pause=paused, seed=seed)
+                for idx, paused in steps]

@@ -574,13 +574,21 @@ def build_training(config_parser, device, logger, resume=None, reset=False):
     (parity: ESR:train_ours_cnt_seq.py:742-807, registry-based)."""
     import torch.nn as nn
 
-    from ..data import SequenceDataLoader
+    from ..data import DeviceSequenceLoader, SequenceDataLoader
     from ..models import build_model
     from ..parallel import wrap_ddp
 
+    def make_loader(dl_cfg):
+        # `device_resident: true` (or a mapping of its options) keeps the
+        # sequences on the device and splats batches there
+        resident = dl_cfg.get("device_resident", False)
+        if resident is True or isinstance(resident, dict):
+            return DeviceSequenceLoader(dl_cfg, device)
+        return SequenceDataLoader(dl_cfg)
+
     cfg = config_parser.config
-    train_loader = SequenceDataLoader(cfg["train_dataloader"])
-    valid_loader = SequenceDataLoader(cfg["valid_dataloader"]) \
+    train_loader = make_loader(cfg["train_dataloader"])
+    valid_loader = make_loader(cfg["valid_dataloader"]) \
         if cfg.get("valid_dataloader") else None
 
     model = build_model(cfg["model"]["name"], **cfg["model"]["args"]).to(device)

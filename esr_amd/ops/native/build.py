@@ -20,7 +20,8 @@ SRC = HERE / "src"
 SOURCES = [SRC / "bindings.cpp", SRC / "deform_conv.hip",
            SRC / "deform_conv_fused.hip", SRC / "gru_gates.hip",
            SRC / "event_ops.hip", SRC / "conv2d.hip", SRC / "redistribute.hip",
-           SRC / "flat_adam.hip", SRC / "stream_ingest.hip"]
+           SRC / "flat_adam.hip", SRC / "stream_ingest.hip",
+           SRC / "batch_splat.hip"]
 
 
 def build(verbose: bool = False) -> str:

@@ -68,6 +68,11 @@ void stream_window_advance(at::Tensor&, const at::Tensor&);
 void stream_splat_ragged(const at::Tensor&, const at::Tensor&,
                          const at::Tensor&, at::Tensor&, int64_t);
 
+// batch_splat.hip
+void evs_batch_splat(const at::Tensor&, const at::Tensor&, at::Tensor&,
+                     int64_t, int64_t, int64_t);
+int64_t evs_batch_splat_chunk();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
         "modulated deformable conv forward (gfx950)");
@@ -111,5 +116,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stream_splat_ragged", &stream_splat_ragged,
         "splat concatenated per-stream LR event windows into the newest "
         "frame of a [seqn,S,2,kH,kW] buffer");
+  m.def("evs_batch_splat", &evs_batch_splat,
+        "splat a batch of packed event windows (jobs read from a device "
+        "tensor) into [J,2,kH,kW] count planes, in place");
+  m.def("evs_batch_splat_chunk", &evs_batch_splat_chunk,
+        "events one block of evs_batch_splat covers");
   m.attr("gfx_arch") = "gfx950";
 }
