@@ -16,16 +16,17 @@ from __future__ import annotations
 
 import torch
 
+from .capture import unwrap
+
 __all__ = ["save_checkpoint", "Resumer", "load_model_from_checkpoint"]
 
 
 def save_checkpoint(path, config: dict, model, optimizer=None,
                     lr_scheduler=None, trainer_state: dict | None = None,
                     grad_scaler=None):
-    model_sd = model.module.state_dict() if hasattr(model, "module") \
-        else model.state_dict()
     state = {
-        "model": {"name": config["model"]["name"], "states": model_sd},
+        "model": {"name": config["model"]["name"],
+                  "states": unwrap(model).state_dict()},
         "lr_scheduler": {"name": config["lr_scheduler"]["name"],
                          "states": lr_scheduler.state_dict() if lr_scheduler else {}},
         "optimizer": {"name": config["optimizer"]["name"],
@@ -68,8 +69,7 @@ class Resumer:
 
     def resume_model(self, model, section="model"):
         self._check(section)
-        target = model.module if hasattr(model, "module") else model
-        target.load_state_dict(self.ckpt[section]["states"])
+        unwrap(model).load_state_dict(self.ckpt[section]["states"])
 
     def resume_optimizer(self, optimizer, section="optimizer",
                          grad_scaler=None):

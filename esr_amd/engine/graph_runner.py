@@ -16,6 +16,12 @@ With FlatAdam/FlatAdamW (esr_amd/optim) the optimizer's own flat gradient is
 the all-reduced buffer, the backward runs on ``optimizer.scale_loss(loss)``
 and the overflow skip / scale update are device-side parts of the captured
 step; the learning rate is a device scalar refreshed before each replay.
+
+The step body itself is step.py's, shared with the eager trainer; the
+warm-up / roll-back / capture sequence is capture.py's `capture_graph`, and
+the roll-back rule (esr_amd.optim.restore_optimizer) is the same for every
+optimizer: what existed before warm-up gets its values back, what warm-up
+created is zeroed.
 """
 
 from __future__ import annotations
@@ -23,6 +29,10 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
+
+from ..optim import restore_optimizer, snapshot_optimizer, sync_lr
+from .capture import amp_autocast, capture_graph
+from .step import backward_and_step, bptt_loss
 
 __all__ = ["GraphedBPTTStep", "flatten_grads"]
 
@@ -39,8 +49,9 @@ def flatten_grads(params, device, dtype=torch.float32):
 
 
 class GraphedBPTTStep:
-    """Captures loss = sum_w MSE(model(inp_w), gt_w); backward; (all-reduce);
-    optimizer.step() into a replayable hipGraph with static I/O buffers."""
+    """Records one BPTT optimizer step (step.py: `bptt_loss` over all
+    windows, then `backward_and_step` with the flat-gradient all-reduce as
+    its sync) on static I/O buffers into a replayable hipGraph."""
 
     def __init__(self, model, optimizer, flat_grad, n_windows,
                  inp_shape, gt_shape, device, amp_dtype=None,
@@ -54,107 +65,43 @@ class GraphedBPTTStep:
         self.world = world_size
         self.sequence = sequence
         self.seqn = seqn
-        if sequence:
-            # inp_shape = [B, L, C, H, W]; gt_shape = [B, n_windows, C, H, W]
-            self.static_in = [torch.zeros(inp_shape, device=device)]
-            self.static_gt = [torch.zeros(gt_shape, device=device)]
-        else:
-            self.static_in = [torch.zeros(inp_shape, device=device)
-                              for _ in range(n_windows)]
-            self.static_gt = [torch.zeros(gt_shape, device=device)
-                              for _ in range(n_windows)]
+        # sequence: one inp_shape = [B, L, C, H, W] frames tensor and one
+        # gt_shape = [B, n_windows, C, H, W]; otherwise one pair per window
+        n_bufs = 1 if sequence else n_windows
+        self.static_in = [torch.zeros(inp_shape, device=device)
+                          for _ in range(n_bufs)]
+        self.static_gt = [torch.zeros(gt_shape, device=device)
+                          for _ in range(n_bufs)]
         self.graph = None
         self.static_loss = None
         self._warmup = warmup
 
-    def _autocast(self):
-        import contextlib
-        if self.amp_dtype is None:
-            return contextlib.nullcontext()
-        return torch.autocast("cuda", dtype=self.amp_dtype,
-                              cache_enabled=False)
+    def _all_reduce(self):
+        if self.world > 1:
+            dist.all_reduce(self.flat_grad)
+            self.flat_grad.div_(self.world)
 
     def _body(self):
         self.flat_grad.zero_()
-        inner = self.model.module if hasattr(self.model, "module") else self.model
-        inner.reset_states()
-        loss = 0
-        mse = None
-        if self.sequence:
-            with self._autocast():
-                preds = inner.forward_sequence(self.static_in[0], self.seqn)
-            gts = self.static_gt[0]
-            for w, pred in enumerate(preds):
-                mse = F.mse_loss(pred.float(), gts[:, w])
-                loss = loss + mse
-        else:
-            for inp, gt in zip(self.static_in, self.static_gt):
-                with self._autocast():
-                    pred = self.model(inp)
-                mse = F.mse_loss(pred.float(), gt)
-                loss = loss + mse
-        scale_loss = getattr(self.optimizer, "scale_loss", None)
-        (scale_loss(loss) if scale_loss else loss).backward()
-        if self.world > 1:
-            # stays before the optimizer: an inf/NaN survives the sum, so
-            # every rank takes the same skip decision
-            dist.all_reduce(self.flat_grad)
-            self.flat_grad.div_(self.world)
-        self.optimizer.step()
+        inputs, gts = (self.static_in[0], self.static_gt[0]) \
+            if self.sequence else (self.static_in, self.static_gt)
+        loss, mse, _ = bptt_loss(
+            self.model, inputs, gts, sequence=self.sequence, seqn=self.seqn,
+            autocast=amp_autocast(self.amp_dtype, self.device,
+                                  cache_enabled=False),
+            loss_fn=F.mse_loss)
+        backward_and_step(loss, self.optimizer, self._all_reduce)
         return loss, mse
 
-    def _snapshot_state(self):
-        params = [p for g in self.optimizer.param_groups for p in g["params"]]
-        # FlatAdam: device scalars (loss scale, growth tracker, step,
-        # skipped count) and the moments, which a resumed run has loaded
-        self._flat_snapshot = None
-        if hasattr(self.optimizer, "device_state"):
-            opt = self.optimizer
-            self._flat_snapshot = [
-                (buf, buf.detach().clone())
-                for buf in (opt.device_state, opt.exp_avg, opt.exp_avg_sq,
-                            opt.max_exp_avg_sq) if buf is not None]
-        return [p.detach().clone() for p in params], params
-
-    def _restore_state(self, snapshot, params):
-        """Undo the warmup steps: params back to their pre-warmup values and
-        the optimizer state zeroed in place (= never stepped).  In-place so
-        the state tensors the capture records keep their addresses.
-        FlatAdam's moments and device scalars (scale, tracker, step, skipped)
-        go back to their pre-warmup values instead: warm-up steps on garbage
-        data may legitimately overflow and back the scale off."""
-        with torch.no_grad():
-            for p, s in zip(params, snapshot):
-                p.copy_(s)
-            if self._flat_snapshot is not None:
-                for buf, saved in self._flat_snapshot:
-                    buf.copy_(saved)
-                self._flat_snapshot = None
-            for state in self.optimizer.state.values():
-                for v in state.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-
     def capture(self):
-        # warmup on a side stream initializes cuDNN/MIOpen plans, autograd
-        # graph allocations and the capturable optimizer's state TENSORS —
-        # but the real optimizer.step()s it runs would perturb the model
-        # with garbage-gradient updates (advisor finding r1), so snapshot
-        # first and roll back before recording the graph.
-        snapshot, params = self._snapshot_state()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(self._warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._restore_state(snapshot, params)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.static_loss, self.static_mse = self._body()
-        torch.cuda.synchronize()
+        # the warm-up runs initialize MIOpen plans, autograd allocations and
+        # the capturable optimizer's state TENSORS, but their optimizer
+        # steps on garbage data are real (and may overflow and back a loss
+        # scale off): snapshot first, roll back before recording
+        snap = snapshot_optimizer(self.optimizer)
+        self.graph, (self.static_loss, self.static_mse) = capture_graph(
+            self._body, warmup=self._warmup,
+            after_warmup=lambda: restore_optimizer(self.optimizer, snap))
         return self
 
     def run(self, window_inputs, window_gts):
@@ -163,9 +110,7 @@ class GraphedBPTTStep:
                                    window_inputs, window_gts):
             si.copy_(inp, non_blocking=True)
             sg.copy_(gt, non_blocking=True)
-        sync_lr = getattr(self.optimizer, "sync_lr", None)
-        if sync_lr is not None:
-            # lr is a device scalar read by the captured FlatAdam step
-            sync_lr()
+        # FlatAdam's lr is a device scalar read by the captured step
+        sync_lr(self.optimizer)
         self.graph.replay()
         return self.static_loss, self.static_mse

@@ -31,8 +31,9 @@ import warnings
 
 import torch
 
-from ..ops import events as E
 from ..ops.native import get_ext
+from .capture import amp_autocast, capture_graph, state_holder
+from .streaming import counts_to_events
 
 __all__ = ["MultiStreamESR", "window_advance_torch", "splat_ragged_torch"]
 
@@ -109,7 +110,7 @@ class MultiStreamESR:
                 "the torch ingest without graph capture", RuntimeWarning,
                 stacklevel=2)
 
-        holder = self._state_holder()
+        holder = state_holder(self.model)
         lstm = getattr(holder, "lstm", None)
         if getattr(lstm, "recurrent_block_type", None) == "convlstm":
             raise NotImplementedError(
@@ -157,11 +158,6 @@ class MultiStreamESR:
                                        pin_memory=pinned),
                 "done": None}
 
-    def _state_holder(self):
-        inner = self.model.module if hasattr(self.model, "module") \
-            else self.model
-        return getattr(inner, "time_propagate", None)
-
     # -- slots ---------------------------------------------------------
     def open(self) -> int:
         """Claim a free slot; the stream starts with an empty window and a
@@ -195,11 +191,8 @@ class MultiStreamESR:
     # -- the per-tick device work (captured as one graph) --------------
     @torch.no_grad()
     def _forward(self, inp: torch.Tensor) -> torch.Tensor:
-        if self.amp_dtype is not None and self.device.type == "cuda":
-            with torch.autocast("cuda", dtype=self.amp_dtype,
-                                cache_enabled=False):
-                return self.model(inp).float()
-        return self.model(inp)
+        with amp_autocast(self.amp_dtype, self.device, cache_enabled=False):
+            return self.model(inp).float()      # no-op on an fp32 output
 
     @torch.no_grad()
     def _tick_body(self) -> torch.Tensor:
@@ -211,7 +204,7 @@ class MultiStreamESR:
             window_advance_torch(self._buf, self._ctrl)
             splat_ragged_torch(self._events, self._offsets, self._ctrl,
                                self._buf, self.scale)
-        holder = self._state_holder()
+        holder = state_holder(self.model)
         if self._state is not None:
             # rows s and S+s belong to stream s
             reset = (self._ctrl[RESET] != 0).repeat(2).view(-1, 1, 1, 1)
@@ -232,18 +225,8 @@ class MultiStreamESR:
         # and commits nothing, so warm-up runs leave windows and state as
         # they are
         self._control.zero_()
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._tick_body()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._out = self._tick_body()
-        torch.cuda.synchronize(self.device)
-        self._graph = g
+        self._graph, self._out = capture_graph(self._tick_body, warmup=2,
+                                               device=self.device)
 
     # -- serving -------------------------------------------------------
     @torch.no_grad()
@@ -339,11 +322,5 @@ class MultiStreamESR:
         ready = self._run(windows)
         if not ready:
             return {}
-        cnt = self._out[ready].float().round().clamp(min=0)
-        ev = E.redistribute_count(cnt, mode=mode, capacity=capacity)
-        out = {}
-        for i, sid in enumerate(ready):
-            n = int((ev[i, :, 3] != 0).sum()) if capacity is None \
-                else capacity
-            out[sid] = ev[i, :n]
-        return out
+        return dict(zip(ready, counts_to_events(self._out[ready], mode,
+                                                capacity)))

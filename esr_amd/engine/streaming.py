@@ -17,8 +17,18 @@ import torch
 
 from ..ops import events as E
 from ..ops.native import get_ext
+from .capture import amp_autocast, capture_graph, state_holder
 
-__all__ = ["StreamingESR"]
+__all__ = ["StreamingESR", "counts_to_events"]
+
+
+def counts_to_events(cnt: torch.Tensor, mode: str, capacity: int | None):
+    """Predicted count maps [N, 2, kH, kW] -> N HR event streams [n, 4],
+    each trimmed to its events, or to `capacity` rows without a sync."""
+    evs = E.redistribute_count(cnt.float().round().clamp(min=0), mode=mode,
+                               capacity=capacity)
+    return [ev[:int((ev[:, 3] != 0).sum()) if capacity is None else capacity]
+            for ev in evs]
 
 
 class StreamingESR:
@@ -67,20 +77,13 @@ class StreamingESR:
 
     @torch.no_grad()
     def _forward(self, inp: torch.Tensor) -> torch.Tensor:
-        if self.amp_dtype is not None and self.device.type == "cuda":
-            with torch.autocast("cuda", dtype=self.amp_dtype,
-                                cache_enabled=False):
-                return self.model(inp).float()
-        return self.model(inp)
-
-    def _state_holder(self):
-        inner = self.model.module if hasattr(self.model, "module") else self.model
-        return getattr(inner, "time_propagate", None)
+        with amp_autocast(self.amp_dtype, self.device, cache_enabled=False):
+            return self.model(inp).float()      # no-op on an fp32 output
 
     def _graph_body(self):
         # recurrence across replays: the state lives in one static buffer
         # that the captured region reads AND writes back in place
-        holder = self._state_holder()
+        holder = state_holder(self.model)
         holder.state = self._static_state
         out = self._forward(self._static_in)
         self._static_state.copy_(holder.state)
@@ -89,7 +92,7 @@ class StreamingESR:
 
     @torch.no_grad()
     def _forward_graphed(self, inp: torch.Tensor) -> torch.Tensor:
-        holder = self._state_holder()
+        holder = state_holder(self.model)
         if holder is None:
             raise RuntimeError("model has no recurrent state holder")
         if self._graph is None:
@@ -97,23 +100,13 @@ class StreamingESR:
             # run once eagerly to materialize the state shape
             out = self._forward(self._static_in)
             self._static_state = holder.state.detach().clone()
-            # warmup and capture both EXECUTE the body, each advancing the
-            # in-place state buffer — snapshot and restore the live state
+            # the warm-up runs EXECUTE the body, each advancing the in-place
+            # state buffer; capture only records it.  So the live state goes
+            # back between the two, and the first replay starts from it.
             state_snapshot = self._static_state.clone()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._graph_body()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._static_out = self._graph_body()
-            torch.cuda.synchronize()
-            self._static_state.copy_(state_snapshot)
-            holder.state = self._static_state
-            self._graph = g
+            self._graph, self._static_out = capture_graph(
+                self._graph_body, warmup=2,
+                after_warmup=lambda: self._static_state.copy_(state_snapshot))
             return out
         self._static_in.copy_(inp)
         self._graph.replay()
@@ -148,7 +141,4 @@ class StreamingESR:
         cnt = self.push(events)
         if cnt is None:
             return None
-        ev = E.redistribute_count(cnt.float().round().clamp(min=0)[None],
-                                  mode=mode, capacity=capacity)[0]
-        n = int((ev[:, 3] != 0).sum()) if capacity is None else capacity
-        return ev[:n]
+        return counts_to_events(cnt[None], mode, capacity)[0]

@@ -23,13 +23,15 @@ from __future__ import annotations
 import math
 
 import torch
-import torch.nn.functional as F
 
 from ..config import build_lr_scheduler, build_optimizer
 from ..config.parser import FLAT_OPTIMIZERS
+from ..optim import flat_grad_of, loss_scale_stats
 from ..parallel import get_rank, reduce_tensor
 from ..utils import MetricTracker, MetricWriter
+from .capture import amp_autocast
 from .checkpoint import Resumer, save_checkpoint
+from .step import backward_and_step, bptt_loss
 
 __all__ = ["Trainer", "loss_scale_plan"]
 
@@ -151,15 +153,6 @@ class Trainer:
 
     # ---------------- core step ----------------
 
-    def _unwrapped(self):
-        return self.model.module if hasattr(self.model, "module") else self.model
-
-    def _autocast(self):
-        if self.amp_dtype is not None and self.device.type == "cuda":
-            return torch.autocast("cuda", dtype=self.amp_dtype)
-        import contextlib
-        return contextlib.nullcontext()
-
     def _get_graph_step(self, inputs_seq):
         """Build (or fetch) the captured BPTT step for this batch shape."""
         from ..parallel import get_world_size
@@ -176,10 +169,9 @@ class Trainer:
         key = (shared, n_windows, inp_shape, gt_shape)
         if self._graph_step is not None and self._graph_step[0] == key:
             return self._graph_step[1]
-        if hasattr(self.optimizer, "flat_grad"):
-            # FlatAdam already owns the flat gradient the params point into
-            flat = self.optimizer.flat_grad
-        else:
+        # FlatAdam already owns the flat gradient the params point into
+        flat = flat_grad_of(self.optimizer)
+        if flat is None:
             params = [p for p in self.model.parameters() if p.requires_grad]
             flat = flatten_grads(params, self.device)
         runner = GraphedBPTTStep(
@@ -213,12 +205,9 @@ class Trainer:
                     f"hipGraph step failed ({type(e).__name__}: {e}); "
                     f"falling back to eager")
                 self.use_graphs = False
-        if train:
-            self.optimizer.zero_grad(set_to_none=True)
-        self._unwrapped().reset_states()
-        loss = 0
-        mse_loss = None
-        if isinstance(inputs_seq, dict):
+        to_dev = lambda t: t.to(self.device, non_blocking=True)  # noqa: E731
+        shared = isinstance(inputs_seq, dict)
+        if shared:
             # shared-encoder sequence batch (collate='shared'); bypasses the
             # DDP wrapper's forward, so it requires either single process or
             # the graphed step's own all-reduce
@@ -227,40 +216,23 @@ class Trainer:
                     "collate='shared' training under DDP requires "
                     "trainer.hip_graphs (the graphed step all-reduces the "
                     "flat gradient itself)")
-            frames = inputs_seq["frames"].to(self.device, non_blocking=True)
-            gts = inputs_seq["gt_mids"].to(self.device, non_blocking=True)
-            with self._autocast():
-                preds = self._unwrapped().forward_sequence(
-                    frames, inputs_seq["seqn"])
-            for w, pred in enumerate(preds):
-                mse_loss = self.loss_fns["mse"](pred.float(), gts[:, w].float())
-                loss = loss + mse_loss
-            pred = preds[-1]
+            inputs = to_dev(inputs_seq["frames"])
+            gts = to_dev(inputs_seq["gt_mids"])
         else:
-            for inputs in inputs_seq:
-                inp = inputs["inp_scaled_cnt"].to(self.device, non_blocking=True)
-                gt = inputs["gt_cnt"][:, self.mid_idx].to(self.device,
-                                                          non_blocking=True)
-                with self._autocast():
-                    pred = self.model(inp)
-                    if pred.shape[-2:] != gt.shape[-2:]:
-                        pred = F.interpolate(pred, size=gt.shape[-2:],
-                                             mode="bicubic", align_corners=False)
-                    mse_loss = self.loss_fns["mse"](pred.float(), gt.float())
-                loss = loss + mse_loss
+            inputs = [to_dev(w["inp_scaled_cnt"]) for w in inputs_seq]
+            gts = [to_dev(w["gt_cnt"][:, self.mid_idx]) for w in inputs_seq]
         if train:
-            # the scaled loss only drives the backward; the un-scaled loss
-            # is what gets logged and returned
-            if self.grad_scaler is not None:
-                self.grad_scaler.scale(loss).backward()
-                self._sync_grads_if_needed()
-                self.grad_scaler.step(self.optimizer)
-                self.grad_scaler.update()
-            else:
-                scale_loss = getattr(self.optimizer, "scale_loss", None)
-                (scale_loss(loss) if scale_loss else loss).backward()
-                self._sync_grads_if_needed()
-                self.optimizer.step()
+            self.optimizer.zero_grad(set_to_none=True)
+        # the eager step keeps autocast's weight-cast cache (a weight used
+        # several times in one forward is cast once)
+        loss, mse_loss, pred = bptt_loss(
+            self.model, inputs, gts, sequence=shared,
+            seqn=inputs_seq["seqn"] if shared else None,
+            autocast=amp_autocast(self.amp_dtype, self.device),
+            loss_fn=self.loss_fns["mse"])
+        if train:
+            backward_and_step(loss, self.optimizer,
+                              self._sync_grads_if_needed, self.grad_scaler)
         return loss.detach(), mse_loss.detach(), pred.detach()
 
     def _sync_grads_if_needed(self):
@@ -273,8 +245,7 @@ class Trainer:
         if world <= 1 or hasattr(self.model, "module"):
             return
         import torch.distributed as dist
-        flat_grad = getattr(getattr(self, "optimizer", None), "flat_grad",
-                            None)
+        flat_grad = flat_grad_of(getattr(self, "optimizer", None))
         if flat_grad is not None:
             # FlatAdam: every .grad is a view of this one buffer; an inf/NaN
             # survives the sum, so every rank skips the same step
@@ -324,6 +295,32 @@ class Trainer:
         if self.watchdog is not None:
             self.watchdog.beat()
 
+    def _set_epoch(self, epoch):
+        if hasattr(self.train_dataloader, "set_epoch"):
+            # epoch-keyed item seeds + sharded-sampler shuffle
+            self.train_dataloader.set_epoch(epoch)
+        elif self.train_dataloader.dist_sampler is not None:
+            self.train_dataloader.dist_sampler.set_epoch(epoch)
+
+    def _record_train_step(self, step, loss, mse_loss, log, message,
+                           lr=None):
+        """Reduce the step's losses over the ranks; on rank 0 feed the
+        metrics (and the `lr` scalar, if given) at writer step `step` and,
+        when `log`, write ``message(mse, loss)`` and the loss scale."""
+        reduced_mse = reduce_tensor(mse_loss)
+        reduced_loss = reduce_tensor(loss)
+        if get_rank() != 0:
+            return  # before .item(): only rank 0 waits for the device
+        reduced_mse, reduced_loss = reduced_mse.item(), reduced_loss.item()
+        self.writer.set_step(step)
+        self.train_metrics.update("train_mse_loss", reduced_mse)
+        self.train_metrics.update("train_loss", reduced_loss)
+        if lr is not None:
+            self.writer.add_scalar("learning_rate", lr)
+        if log:
+            self.logger.info(message(reduced_mse, reduced_loss))
+            self._log_loss_scale()
+
     def iteration_based_training(self):
         self.model.train()
         self.train_metrics.reset()
@@ -331,11 +328,7 @@ class Trainer:
         epoch = 0
         done = False
         while not done:
-            if hasattr(self.train_dataloader, "set_epoch"):
-                # epoch-keyed item seeds + sharded-sampler shuffle
-                self.train_dataloader.set_epoch(epoch)
-            elif self.train_dataloader.dist_sampler is not None:
-                self.train_dataloader.dist_sampler.set_epoch(epoch)
+            self._set_epoch(epoch)
             for idx, inputs_seq in enumerate(self.train_dataloader):
                 iter_idx = idx + len(self.train_dataloader) * epoch \
                     + self.start_iteration
@@ -343,21 +336,15 @@ class Trainer:
                 loss, mse_loss, pred = self.bptt_step(inputs_seq, train=True)
                 self._beat()
 
-                reduced_mse = reduce_tensor(mse_loss)
-                reduced_loss = reduce_tensor(loss)
-
+                lr = self.lr_scheduler.get_last_lr()[0]
+                self._record_train_step(
+                    iter_idx, loss, mse_loss, lr=lr,
+                    log=iter_idx % self.train_log_step == 0,
+                    message=lambda mse, loss: (
+                        f"Train epoch {epoch + 1} iter {iter_idx}/"
+                        f"{self.iterations} mse {mse:.4e} "
+                        f"loss {loss:.4e} lr {lr:.3e}"))
                 if get_rank() == 0:
-                    self.writer.set_step(iter_idx)
-                    self.train_metrics.update("train_mse_loss", reduced_mse.item())
-                    self.train_metrics.update("train_loss", reduced_loss.item())
-                    lr = self.lr_scheduler.get_last_lr()[0]
-                    self.writer.add_scalar("learning_rate", lr)
-                    if iter_idx % self.train_log_step == 0:
-                        self.logger.info(
-                            f"Train epoch {epoch + 1} iter {iter_idx}/"
-                            f"{self.iterations} mse {reduced_mse.item():.4e} "
-                            f"loss {reduced_loss.item():.4e} lr {lr:.3e}")
-                        self._log_loss_scale()
                     self._maybe_visualize(iter_idx, inputs_seq, pred)
 
                 if self.do_validation and iter_idx % self.valid_step == 0 \
@@ -396,27 +383,18 @@ class Trainer:
 
     def epoch_based_training(self):
         for epoch in range(self.start_epoch, self.epochs + 1):
-            if hasattr(self.train_dataloader, "set_epoch"):
-                self.train_dataloader.set_epoch(epoch)
-            elif self.train_dataloader.dist_sampler is not None:
-                self.train_dataloader.dist_sampler.set_epoch(epoch)
+            self._set_epoch(epoch)
             self.model.train()
             self.train_metrics.reset()
             for idx, inputs_seq in enumerate(self.train_dataloader):
                 loss, mse_loss, _ = self.bptt_step(inputs_seq, train=True)
                 self._beat()
-                reduced_mse = reduce_tensor(mse_loss)
-                reduced_loss = reduce_tensor(loss)
-                if get_rank() == 0:
-                    step = (epoch - 1) * len(self.train_dataloader) + idx
-                    self.writer.set_step(step)
-                    self.train_metrics.update("train_mse_loss", reduced_mse.item())
-                    self.train_metrics.update("train_loss", reduced_loss.item())
-                    if idx % self.train_log_step == 0:
-                        self.logger.info(
-                            f"Train epoch {epoch} [{idx}/{len(self.train_dataloader)}]"
-                            f" mse {reduced_mse.item():.4e}")
-                        self._log_loss_scale()
+                self._record_train_step(
+                    (epoch - 1) * len(self.train_dataloader) + idx,
+                    loss, mse_loss, log=idx % self.train_log_step == 0,
+                    message=lambda mse, loss: (
+                        f"Train epoch {epoch} "
+                        f"[{idx}/{len(self.train_dataloader)}] mse {mse:.4e}"))
             log = self.train_metrics.result()
             if self.do_validation and epoch % self.valid_step == 0:
                 with torch.no_grad():
@@ -435,12 +413,7 @@ class Trainer:
         """(loss scale, skipped steps or None) of the active scaler, or None
         when loss scaling is off.  Reading synchronizes with the device:
         call at logging cadence only."""
-        if getattr(self.optimizer, "loss_scaling", False):
-            return (self.optimizer.loss_scale_value,
-                    self.optimizer.skipped_steps)
-        if self.grad_scaler is not None:
-            return self.grad_scaler.get_scale(), None
-        return None
+        return loss_scale_stats(self.optimizer, self.grad_scaler)
 
     def _log_loss_scale(self):
         stats = self.loss_scale_stats()

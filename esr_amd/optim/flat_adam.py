@@ -175,6 +175,14 @@ class FlatAdam(Optimizer):
         skipped, bias corrections); snapshot/restore with clone()/copy_()."""
         return self._state
 
+    def state_buffers(self):
+        """Every tensor a step writes besides the parameters: the device
+        scalars and the moments (esr_amd.optim.snapshot_optimizer)."""
+        bufs = [self._state, self.exp_avg, self.exp_avg_sq]
+        if self.max_exp_avg_sq is not None:
+            bufs.append(self.max_exp_avg_sq)
+        return bufs
+
     # reading these synchronizes: logging cadence only
     @property
     def loss_scale_value(self) -> float:

@@ -45,6 +45,7 @@ def build_arm(name, device):
     """Model params + seeded grads + optimizer for one arm; returns
     (optimizer, numel, captured graph)."""
     import torch
+    from esr_amd.engine.capture import capture_graph
     from esr_amd.models import build_model
     from esr_amd.optim import FlatAdam
 
@@ -67,17 +68,7 @@ def build_arm(name, device):
         with torch.no_grad():
             for p, g in zip(params, grads):
                 p.grad.copy_(g * scale)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(3):
-            opt.step()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        opt.step()
-    torch.cuda.synchronize()
+    graph, _ = capture_graph(opt.step, warmup=3)
     return opt, numel, graph
 
 

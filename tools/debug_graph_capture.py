@@ -9,6 +9,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 import torch
 
+from esr_amd.engine.capture import capture_graph
+from esr_amd.engine.graph_runner import flatten_grads
 from esr_amd.models import build_model
 from esr_amd.ops.native import require_ext
 
@@ -16,19 +18,9 @@ require_ext()
 dev = torch.device("cuda:0")
 
 
-def try_capture(name, warmup_fn, capture_fn):
+def try_capture(name, fn):
     try:
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(3):
-                warmup_fn()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            capture_fn()
-        torch.cuda.synchronize()
+        g, _ = capture_graph(fn, warmup=3)
         g.replay()
         torch.cuda.synchronize()
         print(f"[OK]   {name}")
@@ -42,7 +34,7 @@ def try_capture(name, warmup_fn, capture_fn):
 # stage 1: plain conv fwd
 m1 = torch.nn.Conv2d(2, 8, 3, padding=1).to(dev)
 x1 = torch.randn(8, 2, 64, 64, device=dev)
-try_capture("conv fwd", lambda: m1(x1), lambda: m1(x1))
+try_capture("conv fwd", lambda: m1(x1))
 
 # stage 2: ESRNet fwd fp32
 m = build_model("ESRNet", inch=2, basech=8, num_frame=3,
@@ -55,7 +47,7 @@ def fwd():
     return m(x)
 
 
-try_capture("ESRNet fwd fp32", fwd, fwd)
+try_capture("ESRNet fwd fp32", fwd)
 
 # stage 2b: submodules isolated
 head = m.head
@@ -63,7 +55,7 @@ fe = m.feat_extract
 tp = m.time_propagate
 sf = m.spacetime_fuse
 xf = torch.randn(6, 2, 128, 128, device=dev)
-try_capture("head+encoder", lambda: fe(head(xf)), lambda: fe(head(xf)))
+try_capture("head+encoder", lambda: fe(head(xf)))
 deep = torch.randn(2, 3, 64, 16, 16, device=dev)
 
 
@@ -72,20 +64,15 @@ def run_tp():
     return tp(deep)
 
 
-try_capture("time_propagate", run_tp, run_tp)
+try_capture("time_propagate", run_tp)
 feats_list = [torch.randn(6, 64, 16, 16, device=dev),
               torch.randn(6, 32, 32, 32, device=dev),
               torch.randn(6, 16, 64, 64, device=dev)]
-try_capture("stfusion", lambda: sf(deep, feats_list),
-            lambda: sf(deep, feats_list))
+try_capture("stfusion", lambda: sf(deep, feats_list))
 
 # stage 3: fwd+bwd fp32
 params = [p for p in m.parameters() if p.requires_grad]
-flat = torch.zeros(sum(p.numel() for p in params), device=dev)
-off = 0
-for p in params:
-    p.grad = flat[off:off + p.numel()].view_as(p)
-    off += p.numel()
+flat = flatten_grads(params, dev)
 
 
 def fwd_bwd():
@@ -95,7 +82,7 @@ def fwd_bwd():
     loss.backward()
 
 
-try_capture("ESRNet fwd+bwd fp32", fwd_bwd, fwd_bwd)
+try_capture("ESRNet fwd+bwd fp32", fwd_bwd)
 
 # stage 4: + capturable Adam
 opt = torch.optim.Adam(params, lr=1e-3, weight_decay=1e-4, amsgrad=True,
@@ -107,7 +94,7 @@ def full():
     opt.step()
 
 
-try_capture("fwd+bwd+Adam", full, full)
+try_capture("fwd+bwd+Adam", full)
 
 
 # stage 5: bf16 autocast fwd+bwd
@@ -119,5 +106,5 @@ def fwd_bwd_amp():
     (y.float() ** 2).mean().backward()
 
 
-try_capture("fwd+bwd bf16 autocast", fwd_bwd_amp, fwd_bwd_amp)
+try_capture("fwd+bwd bf16 autocast", fwd_bwd_amp)
 print("done")
