@@ -16,6 +16,15 @@ ESR:models/DCNv2/src/cuda/dcn_v2_cuda.cu:20-216).  Here:
     run natively (16-bit loads, fp32 compute); ESR_NATIVE_FP16=0 sends
     fp16 through fp32 islands instead.  The opt-in fused MFMA forward
     (ESR_DCN_FUSED=1) is fp32-only.
+  * The backward has two paths for the input / offset / mask grads,
+    chosen per call by ``dcn_bwd_path``: "fused" (one kernel, the group's
+    input-grad planes summed in LDS; needs (C/dg)*H*W*4 B <= 64 KiB) and
+    "split" (global-atomic col2im + cast + coordinate kernel).  The
+    default takes the fused kernel wherever it applies; ESR_DCN_BWD=split
+    restores the split path for A/B runs, and ``stats`` counts what ran.
+  * The forward's im2col columns are saved for the weight-grad GEMM
+    (B*C*K*Ho*Wo elements held until the backward); ESR_DCN_SAVE_COLS=0
+    rebuilds them in the backward instead.
 
 Layout conventions (identical to the reference kernels):
   offset: [B, dg*2*kh*kw, Ho, Wo] — per deformable group, per kernel index k
@@ -26,14 +35,17 @@ Layout conventions (identical to the reference kernels):
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 import torch.nn as nn
 
 from .conv import native_fp16_enabled
-from .native import get_ext
+from .native import get_ext, require_ext
 
-__all__ = ["modulated_deform_conv2d", "DeformAlign2d"]
+__all__ = ["modulated_deform_conv2d", "DeformAlign2d",
+           "deform_conv2d_backward", "dcn_bwd_fused_applicable",
+           "dcn_bwd_path"]
 
 
 def _pair(v):
@@ -97,6 +109,66 @@ def _deform_conv2d_torch(input, offset, mask, weight, bias,
     return out
 
 
+# The fused backward keeps one deformable group's input-grad planes in LDS
+# as fp32; 64 KiB is what a block may ask for without opting in to more.
+BWD_FUSED_LDS_MAX = 64 * 1024
+
+# dispatch telemetry, as ops/conv.py's: which backward path each call took
+# and whether it reused the forward's columns
+stats = {"bwd_fused": 0, "bwd_split": 0, "bwd_cols_saved": 0}
+
+
+def dcn_bwd_fused_applicable(C, dg, H, W):
+    """Whether the fused backward kernel covers an input of C channels in dg
+    deformable groups on an H x W image: the group's C/dg fp32 planes must
+    fit in LDS.  deform_conv.hip checks the same rule (dcn_bwd_fused_fits)."""
+    return C % dg == 0 and (C // dg) * H * W * 4 <= BWD_FUSED_LDS_MAX
+
+
+def dcn_bwd_path(C, dg, H, W, path="auto"):
+    """Resolve a backward path selector to "fused" or "split".  "auto"
+    follows ESR_DCN_BWD (fused / split) when set, else takes the fused
+    kernel wherever it applies; an explicit selector wins over the
+    environment.  "fused" on a shape it does not cover is an error."""
+    if path not in ("auto", "fused", "split"):
+        raise ValueError(f"DCN backward path {path!r}: auto, fused or split")
+    if path == "auto":
+        path = os.environ.get("ESR_DCN_BWD", "auto")
+        if path not in ("auto", "fused", "split"):
+            raise ValueError(f"ESR_DCN_BWD={path!r}: auto, fused or split")
+    fits = dcn_bwd_fused_applicable(C, dg, H, W)
+    if path == "fused" and not fits:
+        raise ValueError(
+            f"DCN fused backward needs (C/dg)*H*W*4 B <= {BWD_FUSED_LDS_MAX}; "
+            f"C={C} dg={dg} {H}x{W} needs {C // max(dg, 1) * H * W * 4}")
+    if path == "auto":
+        path = "fused" if fits else "split"
+    return path
+
+
+def save_cols_enabled():
+    """ESR_DCN_SAVE_COLS=0: drop the forward's im2col columns and rebuild
+    them in the backward (B*C*K*Ho*Wo elements less between the two)."""
+    return os.environ.get("ESR_DCN_SAVE_COLS", "1") != "0"
+
+
+def deform_conv2d_backward(input, offset, mask, weight, grad_out,
+                           stride, padding, dilation, deformable_groups,
+                           cols=None, path="auto"):
+    """The native backward on contiguous GPU tensors: the five grads
+    (input, offset, mask, weight, bias).  `cols` are the forward's columns
+    if the caller kept them; `path` is auto / fused / split."""
+    B, C, H, W = input.shape
+    path = dcn_bwd_path(C, deformable_groups, H, W, path)
+    stats["bwd_" + path] += 1
+    if cols is not None:
+        stats["bwd_cols_saved"] += 1
+    return require_ext().deform_conv2d_backward_cols(
+        input, offset, mask, weight, grad_out, cols,
+        stride[0], stride[1], padding[0], padding[1],
+        dilation[0], dilation[1], deformable_groups, path)
+
+
 class _DeformConvHIP(torch.autograd.Function):
     """Autograd wrapper over the native HIP deformable-conv kernels."""
 
@@ -112,24 +184,29 @@ class _DeformConvHIP(torch.autograd.Function):
         offset = offset.contiguous()
         mask = mask.contiguous()
         weight = weight.contiguous()
-        out = ext.deform_conv2d_forward(
-            input, offset, mask, weight, bias,
-            stride[0], stride[1], padding[0], padding[1],
-            dilation[0], dilation[1], deformable_groups)
-        ctx.save_for_backward(input, offset, mask, weight)
+        geom = (stride[0], stride[1], padding[0], padding[1],
+                dilation[0], dilation[1], deformable_groups)
+        # keep the im2col columns for the weight-grad GEMM unless switched
+        # off; the opt-in fused MFMA forward never builds them
+        if save_cols_enabled() and os.environ.get("ESR_DCN_FUSED") != "1":
+            out, cols = ext.deform_conv2d_forward_cols(
+                input, offset, mask, weight, bias, *geom)
+            ctx.save_for_backward(input, offset, mask, weight, cols)
+        else:
+            out = ext.deform_conv2d_forward(
+                input, offset, mask, weight, bias, *geom)
+            ctx.save_for_backward(input, offset, mask, weight)
         ctx.conf = (stride, padding, dilation, deformable_groups)
         ctx.has_bias = bias is not None
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        input, offset, mask, weight = ctx.saved_tensors
+        input, offset, mask, weight, *cols = ctx.saved_tensors
         stride, padding, dilation, dg = ctx.conf
-        ext = get_ext()
-        gi, go, gm, gw, gb = ext.deform_conv2d_backward(
+        gi, go, gm, gw, gb = deform_conv2d_backward(
             input, offset, mask, weight, grad_out.contiguous(),
-            stride[0], stride[1], padding[0], padding[1],
-            dilation[0], dilation[1], dg)
+            stride, padding, dilation, dg, cols=cols[0] if cols else None)
         return (gi, go, gm, gw, gb if ctx.has_bias else None,
                 None, None, None, None)
 
@@ -152,9 +229,9 @@ def modulated_deform_conv2d(input, offset, mask, weight, bias=None,
         if input.dtype == torch.bfloat16 or (
                 input.dtype == torch.float16 and native_fp16_enabled()):
             # 16-bit-native path: the HIP kernels load bf16/fp16 and compute
-            # fp32 (atomic input-grad accumulates fp32, cast back at the
-            # end) — halves the column-buffer/backward HBM traffic vs the
-            # r1 fp32-island design.
+            # fp32 (the input grad is summed in fp32 and rounded once) —
+            # halves the column-buffer/backward HBM traffic vs the r1
+            # fp32-island design.
             dt = input.dtype
             w16 = weight.to(dt)
             b16 = None if bias is None else bias.to(dt)

@@ -10,6 +10,15 @@ std::vector<at::Tensor> deform_conv2d_backward(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const at::Tensor&,
     int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
+std::vector<at::Tensor> deform_conv2d_forward_cols(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const c10::optional<at::Tensor>&,
+    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
+std::vector<at::Tensor> deform_conv2d_backward_cols(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const c10::optional<at::Tensor>&,
+    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+    const std::string&);
 at::Tensor deform_conv2d_forward_fused(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const c10::optional<at::Tensor>&, int64_t);
@@ -78,6 +87,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "modulated deformable conv forward (gfx950)");
   m.def("deform_conv2d_backward", &deform_conv2d_backward,
         "modulated deformable conv backward (gfx950, batched)");
+  m.def("deform_conv2d_forward_cols", &deform_conv2d_forward_cols,
+        "im2col + GEMM forward; returns (out, cols) for the backward to reuse");
+  m.def("deform_conv2d_backward_cols", &deform_conv2d_backward_cols,
+        "backward with optional saved columns and a path selector "
+        "(auto / fused / split)");
   m.def("deform_im2col", &deform_im2col_debug,
         "deformable im2col (test hook)");
   m.def("deform_conv2d_forward_fused", &deform_conv2d_forward_fused,

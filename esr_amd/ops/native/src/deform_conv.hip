@@ -12,6 +12,15 @@
 //     and broadcast across the group's channels via the thread mapping
 //     (channel is the slowest index, so the offset reads of neighbouring
 //     threads coalesce and hit L2 for the channel repeats).
+//   * backward: where a deformable group's input-grad planes fit in LDS
+//     (cpg*H*W*4 B <= 64 KiB) one fused kernel, dcn_bwd_fused_kernel, sums
+//     the input grad on chip and writes the offset and mask grads in the
+//     same pass: no global atomics, no fp32 scratch, no cast.  Larger
+//     planes keep the split path: col2im with global fp32 atomics
+//     (LDS-tiled for fp32 3x3/s1/p1) + cast + col2im_coord.
+//   * the forward can hand its im2col columns to the backward
+//     (deform_conv2d_forward_cols / deform_conv2d_backward_cols), so the
+//     weight-grad GEMM does not rebuild them.
 //
 // Layout (same convention as the reference kernels):
 //   offset [B, dg*2*K, Ho, Wo]  (per group: 2k = h-offset, 2k+1 = w-offset)
@@ -24,34 +33,69 @@
 
 namespace {
 
+// The four integer neighbours of a sample point, zero outside the image.
+// This and the three functions below are the one definition of the
+// boundary rules; every kernel in this file samples through them.
+struct DcnCorners { float v00, v01, v10, v11; };
+
 template <typename T>
-ESR_INLINE float bilinear_sample(const T* __restrict__ im, int H, int W,
-                                 float h, float w) {
-  // zero-padded bilinear; caller guarantees h > -1 && w > -1 && h < H && w < W
-  int h0 = (int)floorf(h);
-  int w0 = (int)floorf(w);
-  float lh = h - h0, lw = w - w0;
+ESR_INLINE DcnCorners load_corners(const T* __restrict__ im, int H, int W,
+                                   int h0, int w0) {
+  // Every corner is loaded, from index 0 where it lies outside, and
+  // selected afterwards: a load under its own branch makes hipcc wait for
+  // it before the next one is issued, and a kernel that samples per
+  // channel then runs at one memory latency per corner.
+  const bool top = h0 >= 0, bot = h0 + 1 < H;
+  const bool lft = w0 >= 0, rgt = w0 + 1 < W;
+  const int at = h0 * W + w0;
+  const float a00 = esr_to_f32(im[top && lft ? at : 0]);
+  const float a01 = esr_to_f32(im[top && rgt ? at + 1 : 0]);
+  const float a10 = esr_to_f32(im[bot && lft ? at + W : 0]);
+  const float a11 = esr_to_f32(im[bot && rgt ? at + W + 1 : 0]);
+  DcnCorners v;
+  v.v00 = top && lft ? a00 : 0.f;
+  v.v01 = top && rgt ? a01 : 0.f;
+  v.v10 = bot && lft ? a10 : 0.f;
+  v.v11 = bot && rgt ? a11 : 0.f;
+  return v;
+}
+
+// lh, lw: fractional parts of the sample coordinates
+ESR_INLINE float bilinear_sample(const DcnCorners& v, float lh, float lw) {
   float hh = 1.f - lh, hw = 1.f - lw;
-  float v00 = (h0 >= 0 && w0 >= 0) ? esr_to_f32(im[h0 * W + w0]) : 0.f;
-  float v01 = (h0 >= 0 && w0 + 1 < W) ? esr_to_f32(im[h0 * W + w0 + 1]) : 0.f;
-  float v10 = (h0 + 1 < H && w0 >= 0) ? esr_to_f32(im[(h0 + 1) * W + w0]) : 0.f;
-  float v11 = (h0 + 1 < H && w0 + 1 < W) ? esr_to_f32(im[(h0 + 1) * W + w0 + 1]) : 0.f;
-  return hh * hw * v00 + hh * lw * v01 + lh * hw * v10 + lh * lw * v11;
+  return hh * hw * v.v00 + hh * lw * v.v01 + lh * hw * v.v10 + lh * lw * v.v11;
 }
 
 // gradient of bilinear_sample wrt the sample coordinates
+ESR_INLINE float coord_grad_h(const DcnCorners& v, float lw) {
+  return (v.v10 - v.v00) * (1.f - lw) + (v.v11 - v.v01) * lw;
+}
+
+ESR_INLINE float coord_grad_w(const DcnCorners& v, float lh) {
+  return (v.v01 - v.v00) * (1.f - lh) + (v.v11 - v.v10) * lh;
+}
+
+// a sample at (h, w) touches the image at all
+ESR_INLINE bool sample_in_range(float h, float w, int H, int W) {
+  return h > -1 && w > -1 && h < H && w < W;
+}
+
+template <typename T>
+ESR_INLINE float bilinear_sample(const T* __restrict__ im, int H, int W,
+                                 float h, float w) {
+  // zero-padded bilinear; caller guarantees sample_in_range(h, w, H, W)
+  int h0 = (int)floorf(h);
+  int w0 = (int)floorf(w);
+  return bilinear_sample(load_corners(im, H, W, h0, w0), h - h0, w - w0);
+}
+
 template <typename T>
 ESR_INLINE float coord_grad_h(const T* __restrict__ im, int H, int W,
                               float h, float w) {
   if (h <= -1 || w <= -1 || h >= H || w >= W) return 0.f;
   int h0 = (int)floorf(h);
   int w0 = (int)floorf(w);
-  float lw = w - w0, hw = 1.f - lw;
-  float v00 = (h0 >= 0 && w0 >= 0) ? esr_to_f32(im[h0 * W + w0]) : 0.f;
-  float v01 = (h0 >= 0 && w0 + 1 < W) ? esr_to_f32(im[h0 * W + w0 + 1]) : 0.f;
-  float v10 = (h0 + 1 < H && w0 >= 0) ? esr_to_f32(im[(h0 + 1) * W + w0]) : 0.f;
-  float v11 = (h0 + 1 < H && w0 + 1 < W) ? esr_to_f32(im[(h0 + 1) * W + w0 + 1]) : 0.f;
-  return (v10 - v00) * hw + (v11 - v01) * lw;
+  return coord_grad_h(load_corners(im, H, W, h0, w0), w - w0);
 }
 
 template <typename T>
@@ -60,12 +104,7 @@ ESR_INLINE float coord_grad_w(const T* __restrict__ im, int H, int W,
   if (h <= -1 || w <= -1 || h >= H || w >= W) return 0.f;
   int h0 = (int)floorf(h);
   int w0 = (int)floorf(w);
-  float lh = h - h0, hh = 1.f - lh;
-  float v00 = (h0 >= 0 && w0 >= 0) ? esr_to_f32(im[h0 * W + w0]) : 0.f;
-  float v01 = (h0 >= 0 && w0 + 1 < W) ? esr_to_f32(im[h0 * W + w0 + 1]) : 0.f;
-  float v10 = (h0 + 1 < H && w0 >= 0) ? esr_to_f32(im[(h0 + 1) * W + w0]) : 0.f;
-  float v11 = (h0 + 1 < H && w0 + 1 < W) ? esr_to_f32(im[(h0 + 1) * W + w0 + 1]) : 0.f;
-  return (v01 - v00) * hh + (v11 - v10) * lh;
+  return coord_grad_w(load_corners(im, H, W, h0, w0), h - h0);
 }
 
 struct DcnGeom {
@@ -109,9 +148,12 @@ __global__ void dcn_im2col_kernel(
         const float m = esr_to_f32(msk_p[k * HoWo + pix]);
         const float h_im = h_in + i * g.dh + off_h;
         const float w_im = w_in + j * g.dw + off_w;
-        float val = 0.f;
-        if (h_im > -1 && w_im > -1 && h_im < g.H && w_im < g.W)
-          val = bilinear_sample(im_p, g.H, g.W, h_im, w_im);
+        // sampled without a branch (at the origin when the point is
+        // outside), so the taps' loads can overlap
+        const bool ok = sample_in_range(h_im, w_im, g.H, g.W);
+        const float s = bilinear_sample(im_p, g.H, g.W, ok ? h_im : 0.f,
+                                        ok ? w_im : 0.f);
+        const float val = ok ? s : 0.f;
         col_p[(long long)k * HoWo] = esr_from_f32<T>(val * m);
       }
     }
@@ -121,7 +163,7 @@ __global__ void dcn_im2col_kernel(
 // --------------------------------------------------- col2im (LDS-tiled)
 // grad wrt input for the 3x3/stride1/pad1 shape: one block per
 // (b, c, 16x16 output tile).  Corner contributions that land inside the
-// tile's input region (+/- HALO) accumulate via fast LDS atomics and are
+// tile's input region (+/- HALO) accumulate via LDS float atomics and are
 // flushed once per block (one global atomic per covered input pixel —
 // ~16x fewer HBM atomics than the per-contribution kernel below); corners
 // pushed outside by large learned offsets fall back to device-scope
@@ -313,6 +355,128 @@ __global__ void dcn_col2im_coord_kernel(
   }
 }
 
+// ------------------------------------------- fused backward (LDS planes)
+// grad wrt input, offsets and mask in one pass over col_grad: one block
+// per (b, deformable group).  The group's cpg input-grad planes live in
+// LDS as fp32 (cpg*H*W*4 B, dynamic, zeroed here), so every contribution
+// is an add into LDS (lds_add_f32) and no global atomic is issued.  The
+// plane is the whole image: no halo, no outlier fallback, any stride /
+// dilation / kernel size.  Each (tap, pixel) decodes its offset, mask and
+// bilinear weights once and reuses them for the group's channels; lanes
+// run along wo, so smooth offsets give consecutive LDS addresses per add.
+constexpr int DCN_BWD_FUSED_LDS_MAX = 64 * 1024;
+
+// Float add into LDS by an integer compare-and-swap loop.  Measured on
+// MI355X (profiles/README.md, DCN backward): the DS float add retires one
+// lane at a time, about 204 G lane-adds/s over the whole chip whatever the
+// addresses, which is slower than global float atomics; integer DS
+// atomics run 32x faster.  The loop repeats only for lanes that lost a
+// race for their address, so smooth offsets pass in one round.
+ESR_INLINE void lds_add_f32(float* p, float v) {
+  unsigned int* pi = reinterpret_cast<unsigned int*>(p);
+  unsigned int seen = __hip_atomic_load(pi, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_WORKGROUP);
+  unsigned int expect;
+  do {
+    expect = seen;
+    seen = atomicCAS(pi, expect, __float_as_uint(__uint_as_float(expect) + v));
+  } while (seen != expect);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void dcn_bwd_fused_kernel(
+    const T* __restrict__ col_grad, const T* __restrict__ im,
+    const T* __restrict__ offset, const T* __restrict__ mask, DcnGeom g,
+    T* __restrict__ grad_im, T* __restrict__ grad_offset,
+    T* __restrict__ grad_mask) {
+  extern __shared__ __attribute__((aligned(16))) float dcn_planes[];
+  const int K = g.kh * g.kw;
+  const int HoWo = g.Ho * g.Wo;
+  const int HW = g.H * g.W;
+  const int cpg = g.C / g.dg;
+  const int plane_n = cpg * HW;
+  // blockIdx.x = b * dg + grp; a group's channels are adjacent in memory
+  const long long bg = blockIdx.x;
+
+  for (int i = threadIdx.x; i < plane_n; i += 256) dcn_planes[i] = 0.f;
+  __syncthreads();
+
+  const T* off_p = offset + bg * 2 * K * HoWo;
+  const T* msk_p = mask + bg * K * HoWo;
+  const T* im_g = im + bg * plane_n;
+  const T* cg_g = col_grad + bg * cpg * K * HoWo;
+  T* goff = grad_offset + bg * 2 * K * HoWo;
+  T* gmsk = grad_mask + bg * K * HoWo;
+
+  for (int it = threadIdx.x; it < K * HoWo; it += 256) {
+    const int k = it / HoWo, pix = it % HoWo;
+    const int ho = pix / g.Wo, wo = pix % g.Wo;
+    const int i = k / g.kw, j = k % g.kw;
+    const float off_h = esr_to_f32(off_p[(2 * k) * HoWo + pix]);
+    const float off_w = esr_to_f32(off_p[(2 * k + 1) * HoWo + pix]);
+    const float m = esr_to_f32(msk_p[it]);
+    const float h_im = ho * g.sh - g.ph + i * g.dh + off_h;
+    const float w_im = wo * g.sw - g.pw + j * g.dw + off_w;
+
+    float gh = 0.f, gw = 0.f, gm = 0.f;
+    if (sample_in_range(h_im, w_im, g.H, g.W)) {
+      const int h0 = (int)floorf(h_im);
+      const int w0 = (int)floorf(w_im);
+      const float lh = h_im - h0, lw = w_im - w0;
+      const bool top = h0 >= 0, bot = h0 + 1 < g.H;
+      const bool lft = w0 >= 0, rgt = w0 + 1 < g.W;
+      const float w00 = (1 - lh) * (1 - lw), w01 = (1 - lh) * lw;
+      const float w10 = lh * (1 - lw), w11 = lh * lw;
+      const int at = h0 * g.W + w0;
+      const T* cg_p = cg_g + k * HoWo + pix;
+      // DCN_BWD_CH channels at a time: all their loads are issued before
+      // the first LDS add (the adds sit under lane-divergent branches,
+      // which loads are not moved across), so a chunk costs one memory
+      // latency, not one per channel.  A chunk's tail past cpg re-reads
+      // the last channel and is not used.
+      constexpr int DCN_BWD_CH = 4;
+      for (int c0 = 0; c0 < cpg; c0 += DCN_BWD_CH) {
+        float cg[DCN_BWD_CH];
+        DcnCorners v[DCN_BWD_CH];
+        #pragma unroll
+        for (int u = 0; u < DCN_BWD_CH; ++u) {
+          const int cc = min(c0 + u, cpg - 1);
+          cg[u] = esr_to_f32(cg_p[(long long)cc * K * HoWo]);
+          v[u] = load_corners(im_g + cc * HW, g.H, g.W, h0, w0);
+        }
+        #pragma unroll
+        for (int u = 0; u < DCN_BWD_CH; ++u) {
+          if (c0 + u >= cpg) break;
+          const float gval = cg[u] * m;
+          float* pl = dcn_planes + (c0 + u) * HW + at;
+          if (top && lft) lds_add_f32(&pl[0], w00 * gval);
+          if (top && rgt) lds_add_f32(&pl[1], w01 * gval);
+          if (bot && lft) lds_add_f32(&pl[g.W], w10 * gval);
+          if (bot && rgt) lds_add_f32(&pl[g.W + 1], w11 * gval);
+          gh += gval * coord_grad_h(v[u], lw);
+          gw += gval * coord_grad_w(v[u], lh);
+          gm += cg[u] * bilinear_sample(v[u], lh, lw);
+        }
+      }
+    }
+    goff[(2 * k) * HoWo + pix] = esr_from_f32<T>(gh);
+    goff[(2 * k + 1) * HoWo + pix] = esr_from_f32<T>(gw);
+    gmsk[it] = esr_from_f32<T>(gm);
+  }
+  __syncthreads();
+  // one rounding from the fp32 sum, plain coalesced stores
+  T* gi = grad_im + bg * plane_n;
+  for (int i = threadIdx.x; i < plane_n; i += 256)
+    gi[i] = esr_from_f32<T>(dcn_planes[i]);
+}
+
+// the rule of esr_amd/ops/dcn.py:dcn_bwd_fused_applicable
+bool dcn_bwd_fused_fits(const DcnGeom& g) {
+  return g.C % g.dg == 0 &&
+         (long long)(g.C / g.dg) * g.H * g.W * 4 <= DCN_BWD_FUSED_LDS_MAX;
+}
+
 DcnGeom make_geom(const at::Tensor& input, const at::Tensor& weight,
                   int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
   DcnGeom g;
@@ -360,6 +524,53 @@ at::Tensor dcn_im2col(const at::Tensor& input, const at::Tensor& offset,
   return cols;
 }
 
+// grad wrt input on the split path (global fp32 atomics; LDS-tiled variant
+// for the 3x3/s1/p1 shape; ESR_DCN_TILED=0/1 forces either kernel for A/B
+// timing).  Default is dtype-dependent: fp32 measured 3.0x faster TILED
+// (r1 microbench); bf16 measured faster UNTILED (whole-step A/B, +1.8%:
+// the bf16 col-grad reads halve the per-contribution kernel's traffic
+// while the tiled kernel stays LDS-atomic-bound).  fp16 has bf16's element
+// size and takes the same (untiled) default; not measured separately.
+at::Tensor dcn_col2im_split(const at::Tensor& input, const at::Tensor& offset,
+                            const at::Tensor& mask, const at::Tensor& col_grad,
+                            const DcnGeom& g) {
+  static const int tiled_env = [] {
+    const char* e = getenv("ESR_DCN_TILED");
+    return e == nullptr ? -1 : (e[0] != '0');
+  }();
+  const bool use_tiled = tiled_env >= 0
+      ? tiled_env != 0 : input.scalar_type() == at::kFloat;
+  const int K = g.kh * g.kw;
+  auto stream = at::hip::getCurrentHIPStream();
+  // atomics accumulate in fp32 regardless of the op dtype
+  auto grad_input_f = at::zeros(input.sizes(), input.options()
+                                                   .dtype(at::kFloat));
+  DISPATCH_DCN_DTYPE(input, [&] {
+    if (use_tiled && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 &&
+        g.ph == 1 && g.pw == 1 && g.dh == 1 && g.dw == 1) {
+      const int tiles = ((g.Ho + C2I_TILE - 1) / C2I_TILE) *
+                        ((g.Wo + C2I_TILE - 1) / C2I_TILE);
+      hipLaunchKernelGGL((dcn_col2im_tiled_kernel<scalar_t>),
+                         dim3(tiles, g.C, g.B), dim3(256), 0, stream,
+                         (const scalar_t*)col_grad.data_ptr(),
+                         (const scalar_t*)offset.data_ptr(),
+                         (const scalar_t*)mask.data_ptr(), g,
+                         grad_input_f.data_ptr<float>());
+    } else {
+      long long n = (long long)g.B * g.C * K * g.Ho * g.Wo;
+      hipLaunchKernelGGL((dcn_col2im_kernel<scalar_t>), dim3(esr_grid(n)),
+                         dim3(ESR_BLOCK), 0, stream, n,
+                         (const scalar_t*)col_grad.data_ptr(),
+                         (const scalar_t*)offset.data_ptr(),
+                         (const scalar_t*)mask.data_ptr(), g,
+                         grad_input_f.data_ptr<float>());
+    }
+    return 0;
+  });
+  return input.scalar_type() == at::kFloat
+      ? grad_input_f : grad_input_f.to(input.scalar_type());
+}
+
 bool dcn_dtype_ok(const at::Tensor& t) {
   return t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16 ||
          t.scalar_type() == at::kHalf;
@@ -386,11 +597,12 @@ at::Tensor deform_conv2d_forward_fused(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const c10::optional<at::Tensor>&, int64_t);
 
-at::Tensor deform_conv2d_forward(
+namespace {
+
+DcnGeom dcn_forward_geom(
     const at::Tensor& input, const at::Tensor& offset, const at::Tensor& mask,
-    const at::Tensor& weight, const c10::optional<at::Tensor>& bias,
-    int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-    int64_t dg) {
+    const at::Tensor& weight, int sh, int sw, int ph, int pw, int dh, int dw,
+    int dg) {
   TORCH_CHECK(input.is_cuda() && dcn_dtype_ok(input),
               "deform_conv2d: fp32/bf16/fp16 CUDA tensors required, got ",
               input.scalar_type());
@@ -401,6 +613,37 @@ at::Tensor deform_conv2d_forward(
   TORCH_CHECK(offset.size(1) == g.dg * 2 * g.kh * g.kw, "offset channels");
   TORCH_CHECK(mask.size(1) == g.dg * g.kh * g.kw, "mask channels");
   TORCH_CHECK(g.C % g.dg == 0, "C % deformable_groups != 0");
+  return g;
+}
+
+}  // namespace
+
+// im2col + GEMM forward that also hands back the columns [B, C*K, Ho*Wo]:
+// the weight-grad GEMM of the backward needs exactly these, so a caller
+// that keeps them saves the backward a second im2col.
+std::vector<at::Tensor> deform_conv2d_forward_cols(
+    const at::Tensor& input, const at::Tensor& offset, const at::Tensor& mask,
+    const at::Tensor& weight, const c10::optional<at::Tensor>& bias,
+    int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+    int64_t dg) {
+  auto g = dcn_forward_geom(input, offset, mask, weight, sh, sw, ph, pw, dh,
+                            dw, dg);
+  auto cols = dcn_im2col(input, offset, mask, g);
+  // one batched GEMM: [B, Cout, C*K] x [B, C*K, HoWo]
+  auto w2d = weight.reshape({g.Cout, g.C * g.kh * g.kw});
+  auto out = at::matmul(w2d, cols);  // broadcasts over B -> [B, Cout, HoWo]
+  out = out.reshape({g.B, g.Cout, g.Ho, g.Wo});
+  if (bias.has_value() && bias->defined())
+    out = out + bias->reshape({1, g.Cout, 1, 1});
+  return {out, cols};
+}
+
+at::Tensor deform_conv2d_forward(
+    const at::Tensor& input, const at::Tensor& offset, const at::Tensor& mask,
+    const at::Tensor& weight, const c10::optional<at::Tensor>& bias,
+    int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+    int64_t dg) {
+  dcn_forward_geom(input, offset, mask, weight, sh, sw, ph, pw, dh, dw, dg);
 
   // Measured on gfx950 at the flagship shape (tools/bench_dcn.py,
   // profiles/README.md): split im2col + hipBLASLt GEMM 0.46 ms vs fused
@@ -416,21 +659,25 @@ at::Tensor deform_conv2d_forward(
       dcn_fused_applicable(input, weight, sh, sw, ph, pw, dh, dw, dg))
     return deform_conv2d_forward_fused(input, offset, mask, weight, bias, dg);
 
-  auto cols = dcn_im2col(input, offset, mask, g);
-  // one batched GEMM: [B, Cout, C*K] x [B, C*K, HoWo]
-  auto w2d = weight.reshape({g.Cout, g.C * g.kh * g.kw});
-  auto out = at::matmul(w2d, cols);  // broadcasts over B -> [B, Cout, HoWo]
-  out = out.reshape({g.B, g.Cout, g.Ho, g.Wo});
-  if (bias.has_value() && bias->defined())
-    out = out + bias->reshape({1, g.Cout, 1, 1});
-  return out;
+  return deform_conv2d_forward_cols(input, offset, mask, weight, bias, sh, sw,
+                                    ph, pw, dh, dw, dg)[0];
 }
 
-std::vector<at::Tensor> deform_conv2d_backward(
+// Backward.  `cols` are the forward's columns when the caller kept them
+// (deform_conv2d_forward_cols); without them the im2col runs again.
+// `path` picks the kernels for the input / offset / mask grads:
+//   "fused"  dcn_bwd_fused_kernel; an error where the group's planes do
+//            not fit in LDS (dcn_bwd_fused_fits)
+//   "split"  col2im (atomics) + fp32 scratch + cast + col2im_coord
+//   "auto"   fused where it fits, else split
+// Measured at the flagship shape (bf16, B=768, C=64, 32x32, dg=8): see
+// profiles/README.md, DCN backward.
+std::vector<at::Tensor> deform_conv2d_backward_cols(
     const at::Tensor& input, const at::Tensor& offset, const at::Tensor& mask,
     const at::Tensor& weight, const at::Tensor& grad_out,
+    const c10::optional<at::Tensor>& cols_saved,
     int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
-    int64_t dg) {
+    int64_t dg, const std::string& path) {
   TORCH_CHECK(input.is_contiguous() && offset.is_contiguous() &&
               mask.is_contiguous() && weight.is_contiguous() &&
               grad_out.is_contiguous(),
@@ -449,74 +696,84 @@ std::vector<at::Tensor> deform_conv2d_backward(
   auto go2d = grad_out.reshape({g.B, g.Cout, g.Ho * g.Wo});
   auto w2d = weight.reshape({g.Cout, g.C * K});
 
+  TORCH_CHECK(g.C % g.dg == 0, "C % deformable_groups != 0");
+  TORCH_CHECK(path == "auto" || path == "fused" || path == "split",
+              "deform_conv2d_backward: path must be auto, fused or split, "
+              "got '", path, "'");
+  const bool fits = dcn_bwd_fused_fits(g);
+  TORCH_CHECK(path != "fused" || fits,
+              "deform_conv2d_backward: the fused path keeps a deformable "
+              "group's input-grad planes in LDS and needs (C/dg)*H*W*4 B <= ",
+              DCN_BWD_FUSED_LDS_MAX, "; got ",
+              (long long)(g.C / g.dg) * g.H * g.W * 4,
+              " B (use path=auto or split)");
+  const bool use_fused = path == "fused" || (path == "auto" && fits);
+
   // grad wrt columns: [B, C*K, HoWo] = W^T [C*K, Cout] x go2d (batched)
   auto col_grad = at::matmul(w2d.t(), go2d).contiguous();
 
-  // grad input (atomics; LDS-tiled variant for the 3x3/s1/p1 shape;
-  // ESR_DCN_TILED=0/1 forces either kernel for A/B timing).  Default is
-  // dtype-dependent: fp32 measured 3.0x faster TILED (r1 microbench);
-  // bf16 measured faster UNTILED (whole-step A/B, +1.8%: the bf16
-  // col-grad reads halve the per-contribution kernel's traffic while the
-  // tiled kernel stays LDS-atomic-bound).  fp16 has bf16's element size
-  // and takes the same (untiled) default; not measured separately.
-  static const int tiled_env = [] {
-    const char* e = getenv("ESR_DCN_TILED");
-    return e == nullptr ? -1 : (e[0] != '0');
-  }();
-  const bool use_tiled = tiled_env >= 0
-      ? tiled_env != 0 : input.scalar_type() == at::kFloat;
-  // atomics accumulate in fp32 regardless of the op dtype
-  auto grad_input_f = at::zeros(input.sizes(), input.options()
-                                                   .dtype(at::kFloat));
-  DISPATCH_DCN_DTYPE(input, [&] {
-    if (use_tiled && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 &&
-        g.ph == 1 && g.pw == 1 && g.dh == 1 && g.dw == 1) {
-      const int tiles = ((g.Ho + C2I_TILE - 1) / C2I_TILE) *
-                        ((g.Wo + C2I_TILE - 1) / C2I_TILE);
-      hipLaunchKernelGGL((dcn_col2im_tiled_kernel<scalar_t>),
-                         dim3(tiles, g.C, g.B), dim3(256), 0, stream,
-                         (const scalar_t*)col_grad.data_ptr(),
-                         (const scalar_t*)offset.data_ptr(),
-                         (const scalar_t*)mask.data_ptr(), g,
-                         grad_input_f.data_ptr<float>());
-    } else {
-      long long n = (long long)g.B * g.C * K * g.Ho * g.Wo;
-      hipLaunchKernelGGL((dcn_col2im_kernel<scalar_t>), dim3(esr_grid(n)),
-                         dim3(ESR_BLOCK), 0, stream, n,
-                         (const scalar_t*)col_grad.data_ptr(),
-                         (const scalar_t*)offset.data_ptr(),
-                         (const scalar_t*)mask.data_ptr(), g,
-                         grad_input_f.data_ptr<float>());
-    }
-    return 0;
-  });
-  auto grad_input = input.scalar_type() == at::kFloat
-      ? grad_input_f : grad_input_f.to(input.scalar_type());
-
-  // grad offset + mask
+  at::Tensor grad_input;
   auto grad_offset = at::empty_like(offset);
   auto grad_mask = at::empty_like(mask);
-  DISPATCH_DCN_DTYPE(input, [&] {
-    long long n = (long long)g.B * g.dg * K * g.Ho * g.Wo;
-    hipLaunchKernelGGL((dcn_col2im_coord_kernel<scalar_t>),
-                       dim3(esr_grid(n)), dim3(ESR_BLOCK), 0, stream, n,
-                       (const scalar_t*)col_grad.data_ptr(),
-                       (const scalar_t*)input.data_ptr(),
-                       (const scalar_t*)offset.data_ptr(),
-                       (const scalar_t*)mask.data_ptr(), g,
-                       (scalar_t*)grad_offset.data_ptr(),
-                       (scalar_t*)grad_mask.data_ptr());
-    return 0;
-  });
+  if (use_fused) {
+    grad_input = at::empty_like(input);
+    const size_t lds = (size_t)(g.C / g.dg) * g.H * g.W * sizeof(float);
+    DISPATCH_DCN_DTYPE(input, [&] {
+      hipLaunchKernelGGL((dcn_bwd_fused_kernel<scalar_t>),
+                         dim3(g.B * g.dg), dim3(256), lds, stream,
+                         (const scalar_t*)col_grad.data_ptr(),
+                         (const scalar_t*)input.data_ptr(),
+                         (const scalar_t*)offset.data_ptr(),
+                         (const scalar_t*)mask.data_ptr(), g,
+                         (scalar_t*)grad_input.data_ptr(),
+                         (scalar_t*)grad_offset.data_ptr(),
+                         (scalar_t*)grad_mask.data_ptr());
+      return 0;
+    });
+  } else {
+    grad_input = dcn_col2im_split(input, offset, mask, col_grad, g);
+    DISPATCH_DCN_DTYPE(input, [&] {
+      long long n = (long long)g.B * g.dg * K * g.Ho * g.Wo;
+      hipLaunchKernelGGL((dcn_col2im_coord_kernel<scalar_t>),
+                         dim3(esr_grid(n)), dim3(ESR_BLOCK), 0, stream, n,
+                         (const scalar_t*)col_grad.data_ptr(),
+                         (const scalar_t*)input.data_ptr(),
+                         (const scalar_t*)offset.data_ptr(),
+                         (const scalar_t*)mask.data_ptr(), g,
+                         (scalar_t*)grad_offset.data_ptr(),
+                         (scalar_t*)grad_mask.data_ptr());
+      return 0;
+    });
+  }
 
   // grad weight / bias via batched GEMM (the reference loops per sample,
   // ESR:models/DCNv2/src/cuda/dcn_v2_cuda.cu:150)
-  auto cols = dcn_im2col(input, offset, mask, g);
+  at::Tensor cols;
+  if (cols_saved.has_value() && cols_saved->defined()) {
+    cols = *cols_saved;
+    TORCH_CHECK(cols.is_contiguous() && cols.dim() == 3 &&
+                cols.size(0) == g.B && cols.size(1) == g.C * K &&
+                cols.size(2) == g.Ho * g.Wo &&
+                cols.scalar_type() == input.scalar_type(),
+                "deform_conv2d_backward: saved columns do not match");
+  } else {
+    cols = dcn_im2col(input, offset, mask, g);
+  }
   auto grad_weight = at::bmm(go2d, cols.transpose(1, 2)).sum(0)
                          .reshape(weight.sizes());
   auto grad_bias = grad_out.sum(at::IntArrayRef{0, 2, 3});
 
   return {grad_input, grad_offset, grad_mask, grad_weight, grad_bias};
+}
+
+std::vector<at::Tensor> deform_conv2d_backward(
+    const at::Tensor& input, const at::Tensor& offset, const at::Tensor& mask,
+    const at::Tensor& weight, const at::Tensor& grad_out,
+    int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t dh, int64_t dw,
+    int64_t dg) {
+  return deform_conv2d_backward_cols(input, offset, mask, weight, grad_out,
+                                     c10::nullopt, sh, sw, ph, pw, dh, dw, dg,
+                                     "auto");
 }
 
 at::Tensor deform_im2col_debug(

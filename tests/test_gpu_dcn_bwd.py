@@ -1,0 +1,194 @@
+"""DCN backward on the GPU: the fused kernel (input-grad planes summed in
+LDS, offset / mask grads in the same pass), the saved im2col columns and
+the path choice, against the CPU fp32 autograd oracle
+(`_deform_conv2d_torch`).  Inputs as tests/test_gpu_kernels.py::_dcn_problem:
+offsets randn * scale, mask rand."""
+
+import functools
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ["input", "offset", "mask", "weight", "bias"]
+# run-to-run bound of test_dcn_backward_replay_determinism
+RTOL = ATOL = 1e-5
+
+
+@functools.lru_cache(maxsize=None)
+def _problem(B, C, H, W, Cout, dg, stride=1, pad=1, dil=1, off_scale=2.0,
+             seed=0, dtype=torch.float32):
+    """CPU tensors (input, offset, mask, weight, bias, grad_out), already
+    rounded to `dtype` but held in fp32, and the oracle's five grads.
+    Cached: callers must not modify what they get."""
+    from esr_amd.ops.dcn import _deform_conv2d_torch
+    g = torch.Generator().manual_seed(seed)
+    Ho = (H + 2 * pad - (dil * 2 + 1)) // stride + 1
+    Wo = (W + 2 * pad - (dil * 2 + 1)) // stride + 1
+    args = [torch.randn(B, C, H, W, generator=g),
+            torch.randn(B, dg * 18, Ho, Wo, generator=g) * off_scale,
+            torch.rand(B, dg * 9, Ho, Wo, generator=g),
+            torch.randn(Cout, C, 3, 3, generator=g) * 0.2,
+            torch.randn(Cout, generator=g)]
+    gout = torch.randn(B, Cout, Ho, Wo, generator=g)
+    args = [t.to(dtype).float() for t in args]
+    gout = gout.to(dtype).float()
+    leaves = [t.clone().requires_grad_(True) for t in args]
+    out = _deform_conv2d_torch(*leaves, (stride, stride), (pad, pad),
+                               (dil, dil), dg)
+    out.backward(gout)
+    return args + [gout], [t.grad for t in leaves]
+
+
+def _run(tensors, dg, path, stride=1, pad=1, dil=1, dtype=torch.float32,
+         cols=None):
+    from esr_amd.ops.dcn import deform_conv2d_backward
+    inp, off, msk, w, _, gout = [t.to("cuda", dtype).contiguous()
+                                 for t in tensors]
+    return deform_conv2d_backward(inp, off, msk, w, gout, (stride, stride),
+                                  (pad, pad), (dil, dil), dg, cols=cols,
+                                  path=path)
+
+
+def _rel_errs(grads, ref):
+    return [(g.float().cpu() - r).abs().max().item()
+            / (r.abs().max().item() + 1e-6) for g, r in zip(grads, ref)]
+
+
+def _check_oracle(grads, ref, which=NAMES):
+    errs = dict(zip(NAMES, _rel_errs(grads, ref)))
+    print("rel errs:", {n: f"{errs[n]:.3g}" for n in which})
+    for n in which:
+        assert errs[n] < 1e-3, f"grad_{n} rel err {errs[n]}"
+
+
+@pytest.mark.parametrize("off_scale", [2.0, 8.0])
+def test_fused_fp32_matches_oracle(off_scale):
+    """Odd sizes (partial waves, rows that are no 16-B multiple).  Scale 8
+    puts many samples outside the image or in the (-1, 0) / (H-1, H)
+    border bands."""
+    from esr_amd.ops import dcn
+    tensors, ref = _problem(2, 16, 14, 18, 12, 4, off_scale=off_scale, seed=3)
+    before = dict(dcn.stats)
+    grads = _run(tensors, 4, "fused")
+    assert dcn.stats["bwd_fused"] == before["bwd_fused"] + 1
+    assert dcn.stats["bwd_split"] == before["bwd_split"]
+    _check_oracle(grads, ref)
+
+
+@pytest.mark.parametrize("stride,pad,dil", [(2, 1, 1), (1, 2, 2)])
+def test_fused_stride_and_dilation(stride, pad, dil):
+    tensors, ref = _problem(1, 8, 16, 16, 4, 2, stride=stride, pad=pad,
+                            dil=dil, off_scale=1.0, seed=9)
+    grads = _run(tensors, 2, "fused", stride=stride, pad=pad, dil=dil)
+    _check_oracle(grads, ref, ["input", "offset", "mask"])
+
+
+def test_whole_group_edge():
+    """cpg*H*W*4 of exactly 64 KiB runs fused; 73.7 KB does not: auto takes
+    the split path there, fused is an error, auto still matches."""
+    from esr_amd.ops import dcn
+    from esr_amd.ops.native import require_ext
+    tensors, ref = _problem(1, 8, 32, 64, 4, 1, seed=5)
+    before = dcn.stats["bwd_fused"]
+    _check_oracle(_run(tensors, 1, "auto"), ref)
+    assert dcn.stats["bwd_fused"] == before + 1
+
+    tensors, ref = _problem(1, 8, 48, 48, 4, 1, seed=6)
+    before = dict(dcn.stats)
+    _check_oracle(_run(tensors, 1, "auto"), ref)
+    assert dcn.stats["bwd_split"] == before["bwd_split"] + 1
+    assert dcn.stats["bwd_fused"] == before["bwd_fused"]
+    with pytest.raises(ValueError, match="fused backward needs"):
+        _run(tensors, 1, "fused")
+    # the extension refuses it too, whoever calls
+    inp, off, msk, w, _, gout = [t.cuda() for t in tensors]
+    with pytest.raises(RuntimeError, match="fused path"):
+        require_ext().deform_conv2d_backward_cols(
+            inp, off, msk, w, gout, None, 1, 1, 1, 1, 1, 1, 1, "fused")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_fused_16bit_no_worse_than_split(dtype):
+    """Both paths keep an fp32 sum and round once, so only the add order
+    differs: per grad the fused max-abs error against the fp32 oracle (on
+    the same 16-bit-rounded inputs) is at most 2x the split path's."""
+    tensors, ref = _problem(2, 16, 32, 32, 16, 4, seed=11, dtype=dtype)
+    fused = _run(tensors, 4, "fused", dtype=dtype)
+    split = _run(tensors, 4, "split", dtype=dtype)
+    assert all(g.dtype == dtype for g in fused)
+    ef = [(g.float().cpu() - r).abs().max().item() for g, r in zip(fused, ref)]
+    es = [(g.float().cpu() - r).abs().max().item() for g, r in zip(split, ref)]
+    report = ", ".join(f"{n}: fused {a:.4g} / split {b:.4g}"
+                       for n, a, b in zip(NAMES, ef, es))
+    print(f"DCN backward max-abs errors ({dtype}) -", report)
+    bad = [n for n, a, b in zip(NAMES, ef, es) if not a <= 2 * b]
+    assert not bad, f"fused worse than 2x split on {bad} - {report}"
+
+
+def test_fused_run_to_run():
+    tensors, _ = _problem(2, 16, 32, 32, 8, 4, seed=0)
+    g1 = _run(tensors, 4, "fused")
+    g2 = _run(tensors, 4, "fused")
+    for a, b, n in zip(g1, g2, NAMES):
+        print(f"grad_{n}: {(a != b).sum().item()} of {a.numel()} differ")
+        assert torch.allclose(a, b, atol=ATOL, rtol=RTOL), n
+
+
+@pytest.mark.parametrize("save", ["1", "0"])
+def test_saved_columns_match_recompute(monkeypatch, save):
+    """Grads through modulated_deform_conv2d against the 12-argument entry,
+    which rebuilds the columns: weight and bias bitwise, the rest within
+    the run-to-run bound; the same with saving switched off."""
+    from esr_amd.ops import dcn
+    from esr_amd.ops.native import require_ext
+    monkeypatch.setenv("ESR_DCN_SAVE_COLS", save)
+    tensors, _ = _problem(2, 16, 14, 18, 12, 4, seed=7)
+    *args, gout = [t.cuda() for t in tensors]
+    leaves = [t.clone().requires_grad_(True) for t in args]
+    before = dcn.stats["bwd_cols_saved"]
+    out = dcn.modulated_deform_conv2d(*leaves, stride=1, padding=1,
+                                      dilation=1, deformable_groups=4)
+    out.backward(gout)
+    assert dcn.stats["bwd_cols_saved"] == before + (save == "1")
+    ref = require_ext().deform_conv2d_backward(
+        *args[:4], gout, 1, 1, 1, 1, 1, 1, 4)
+    got = [t.grad for t in leaves]
+    assert torch.equal(got[3], ref[3]), "grad_weight not bitwise"
+    assert torch.equal(got[4], ref[4]), "grad_bias not bitwise"
+    for i in range(3):
+        assert torch.allclose(got[i], ref[i], atol=ATOL, rtol=RTOL), NAMES[i]
+
+
+def test_graph_capture_replays():
+    """Forward + backward of a DeformAlign2d in bf16 captured with the
+    engine's helper: two replays give finite grads equal to the eager run.
+    Capture fails on a synchronise or a host read, so this also shows the
+    path has neither."""
+    from esr_amd.engine.capture import capture_graph
+    from esr_amd.ops import dcn
+    torch.manual_seed(0)
+    m = dcn.DeformAlign2d(16, 16, 3, padding=1, deformable_groups=4) \
+        .cuda().to(torch.bfloat16)
+    x = torch.randn(2, 16, 32, 32, device="cuda").to(torch.bfloat16) \
+        .requires_grad_(True)
+    f = torch.randn(2, 16, 32, 32, device="cuda").to(torch.bfloat16) \
+        .requires_grad_(True)
+    leaves = [x, f] + list(m.parameters())
+
+    def body():
+        out = m(x, f)
+        return torch.autograd.grad(out.float().square().mean(), leaves)
+
+    before = dcn.stats["bwd_fused"]
+    eager = [g.clone() for g in body()]
+    assert dcn.stats["bwd_fused"] == before + 1
+    graph, static = capture_graph(body, warmup=2)
+    for _ in range(2):
+        graph.replay()
+        torch.cuda.synchronize()
+        for got, want in zip(static, eager):
+            assert torch.isfinite(got).all()
+            assert torch.allclose(got.float(), want.float(),
+                                  atol=ATOL, rtol=RTOL)
