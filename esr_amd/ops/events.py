@@ -222,6 +222,8 @@ def redistribute_stack(stack: torch.Tensor, mode: str = "linear",
     and ESR:dataloader/encodings.py:366-463: a cell with value v at bin c
     emits |v| events at that pixel with timestamps in
     (c/C + 1/(100C), (c+1)/C], polarity sign(v); per-item global sort by t.
+    v is rounded first, halves to even (torch.round here, rintf in the
+    kernels), so a cell holding 2.5 emits 2 events on either path.
 
     On GPU with the native extension this runs as one device pipeline
     (prefix scan + scatter + segmented radix sort, redistribute.hip) with

@@ -44,6 +44,7 @@ std::vector<at::Tensor> gru_gates_out_backward(
 at::Tensor splat_count(const at::Tensor&, int64_t, int64_t);
 at::Tensor splat_stack(const at::Tensor&, int64_t, int64_t, int64_t, double,
                        double);
+int64_t grid_cap();
 
 // conv2d.hip
 at::Tensor conv2d_fwd_mfma(const at::Tensor&, const at::Tensor&,
@@ -102,6 +103,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gru_gates_out_backward", &gru_gates_out_backward);
   m.def("splat_count", &splat_count);
   m.def("splat_stack", &splat_stack);
+  m.def("grid_cap", &grid_cap,
+        "work items one grid of a capped grid-stride kernel covers");
   m.def("conv2d_fwd_mfma", &conv2d_fwd_mfma,
         "bf16/fp16 NCHW conv fwd, MFMA implicit GEMM, fused bias+act (gfx950)");
   m.def("conv2d_fwd_valu", &conv2d_fwd_valu,

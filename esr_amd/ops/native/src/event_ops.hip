@@ -53,6 +53,10 @@ __global__ void splat_stack_kernel(long long n, int N, int TB, int H, int W,
 
 }  // namespace
 
+// Work items one launch of a capped grid-stride kernel covers before any
+// thread takes a second iteration (tests size their wrap cases from it).
+int64_t grid_cap() { return (int64_t)ESR_MAX_BLOCKS * ESR_BLOCK; }
+
 at::Tensor splat_count(const at::Tensor& events, int64_t H, int64_t W) {
   TORCH_CHECK(events.is_cuda() && events.scalar_type() == at::kFloat &&
               events.is_contiguous() && events.size(-1) == 4,

@@ -28,7 +28,9 @@ namespace {
 __global__ void redist_counts_kernel(long long n,
                                      const float* __restrict__ stack,
                                      int* __restrict__ counts) {
-  ESR_KERNEL_LOOP(i, n) counts[i] = (int)fabsf(roundf(stack[i]));
+  // rintf: halves to even, as torch.round in the CPU oracle and in the
+  // capacity the Python side computes (roundf rounds halves away from zero)
+  ESR_KERNEL_LOOP(i, n) counts[i] = (int)fabsf(rintf(stack[i]));
 }
 
 ESR_INLINE float u01_hash(unsigned x) {
@@ -47,7 +49,7 @@ __global__ void redist_scatter_kernel(
     long long NC, int C, int Y, int X, int capacity, int mode, unsigned seed,
     float* __restrict__ keys, unsigned* __restrict__ payload) {
   ESR_KERNEL_LOOP(i, ncells) {
-    const float v = roundf(stack[i]);
+    const float v = rintf(stack[i]);
     const int cnt = (int)fabsf(v);
     if (!cnt) continue;
     const int b = (int)(i / NC);

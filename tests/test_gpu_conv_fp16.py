@@ -95,6 +95,14 @@ CASES = [
     (8, 2, 62, 32, 3, 1, "relu"),        # tail class, COCH=2, odd H
     (8, 2, 62, 30, 3, 1, "relu"),        # odd W -> routed to the v1 kernel
     (2, 8, 64, 64, 3, 2, None),          # tiny s2 (valu2 strided segs)
+    (64, 216, 32, 32, 3, 1, None),       # flagship offset/mask conv: 224
+                                         # packed rows, last cout block clamps
+    (32, 64, 18, 70, 3, 2, "relu"),      # MFMA s2: Wo=35 two x-tiles (2nd
+                                         # partial), Ho=9 partial row tile
+    (64, 80, 10, 40, 1, 1, None),        # Cout_p=80, MREP=1, third block
+                                         # half past Cout_p
+    (2, 8, 24, 40, 3, 2, None),          # valu2 s2: Wo=20, 4-wide last strip,
+                                         # misaligned rows
 ]
 
 

@@ -77,6 +77,20 @@ def test_fused_fp32_matches_oracle(off_scale):
     _check_oracle(grads, ref)
 
 
+@pytest.mark.parametrize("C,dg,Cout", [(12, 2, 5), (16, 8, 5)],
+                         ids=["cpg6", "cpg2"])
+def test_fused_fp32_cpg_not_multiple_of_chunk(C, dg, Cout):
+    """The fused kernel loads channels four at a time; with cpg = 6 the
+    second chunk's tail, and with cpg = 2 half of the only chunk, lies past
+    cpg: it re-reads the last channel and must not be added anywhere."""
+    from esr_amd.ops import dcn
+    tensors, ref = _problem(1, C, 9, 11, Cout, dg, off_scale=2.0, seed=13)
+    before = dcn.stats["bwd_fused"]
+    grads = _run(tensors, dg, "fused")
+    assert dcn.stats["bwd_fused"] == before + 1
+    _check_oracle(grads, ref)
+
+
 @pytest.mark.parametrize("stride,pad,dil", [(2, 1, 1), (1, 2, 2)])
 def test_fused_stride_and_dilation(stride, pad, dil):
     tensors, ref = _problem(1, 8, 16, 16, 4, 2, stride=stride, pad=pad,

@@ -151,7 +151,44 @@ class TestGruGates:
         assert torch.allclose(h2g.cpu(), h2, atol=1e-4)
 
 
+def splat_problem(B, N, TB, H, W, seed):
+    """Events [B, N, 4] on the CPU with about 1/8 out of range and 1/16
+    padding (p = 0), timestamps (k + 0.5) / (16*TB): mid-bin, clear of every
+    edge, so any binning rule puts event k into bin k // 16.  Returns the
+    events and the exact integer references: counts [B, 2, H, W] and signed
+    stack [B, TB, H, W] (int64)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randint(-2, W + 2, (B, N), generator=g)
+    y = torch.randint(-2, H + 2, (B, N), generator=g)
+    k = torch.randint(0, 16 * TB, (B, N), generator=g)
+    p = torch.randint(0, 2, (B, N), generator=g) * 2 - 1
+    p[torch.rand(B, N, generator=g) < 1 / 16] = 0
+    ev = torch.stack([x.float(), y.float(), (k.float() + 0.5) / (16 * TB),
+                      p.float()], dim=2).contiguous()
+    live = (x >= 0) & (x < W) & (y >= 0) & (y < H) & (p != 0)
+    assert int((~live).sum()) > 0 and int((p == 0).sum()) > 0
+    b = torch.arange(B).view(B, 1).expand(B, N)
+    cnt = torch.zeros(B, 2, H, W, dtype=torch.int64)
+    stack = torch.zeros(B, TB, H, W, dtype=torch.int64)
+    bl, xl, yl, pl, kl = b[live], x[live], y[live], p[live], k[live]
+    cnt.index_put_((bl, (pl < 0).long(), yl, xl), torch.ones_like(pl),
+                   accumulate=True)
+    stack.index_put_((bl, kl // 16, yl, xl), pl, accumulate=True)
+    return ev, cnt, stack
+
+
 class TestSplat:
+    def test_splat_stack_per_bin_exact(self, ext):
+        """Every bin of splat_stack, exactly (the test below only compares
+        sums over bins), with out-of-range and p = 0 events in the feed."""
+        B, N, TB, H, W = 2, 4096, 4, 16, 16
+        ev, cnt, stack = splat_problem(B, N, TB, H, W, seed=5)
+        out = ext.splat_stack(ev.cuda(), TB, H, W, 0.0, 1.0)
+        assert torch.equal(out.cpu(), stack.float()), \
+            f"{int((out.cpu() != stack.float()).sum())} cells differ"
+        out_c = ext.splat_count(ev.cuda(), H, W)
+        assert torch.equal(out_c.cpu(), cnt.float())
+
     def test_splat_count_matches_torch(self, ext):
         from esr_amd.ops import events_to_channels
         g = torch.Generator().manual_seed(0)

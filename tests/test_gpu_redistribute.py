@@ -40,6 +40,46 @@ def test_redistribute_gpu_matches_cpu_oracle():
             assert torch.equal(hc, hg)
 
 
+def half_integer_stack():
+    """[2, 3, 8, 8] stack of half-integers and near-halves, as bf16 rounds
+    them: torch.round takes halves to even (2.5 -> 2, -1.5 -> -2)."""
+    vals = torch.tensor([0.5, -0.5, 1.5, -1.5, 2.5, -2.5, 0.49, 2.51])
+    g = torch.Generator().manual_seed(21)
+    idx = torch.randint(0, len(vals), (2, 3, 8, 8), generator=g)
+    stack = vals[idx].to(torch.bfloat16).float()
+    assert all(bool((stack == v).any()) for v in (0.5, 1.5, 2.5, -2.5))
+    return stack
+
+
+def test_redistribute_halves_round_to_even_like_cpu():
+    """Half-integer cells: the kernels must round as torch.round does in the
+    CPU oracle and in the capacity the dispatcher computes, or the trimmed
+    capacity is too small and events are dropped silently."""
+    from esr_amd.ops.events import redistribute_stack
+    stack = half_integer_stack()
+    cpu = redistribute_stack(stack, mode="linear")
+    gpu = redistribute_stack(stack.to(DEV), mode="linear").cpu()
+    want_len = stack.round().abs().sum(dim=(1, 2, 3)).long()
+    assert cpu.size(1) == int(want_len.max())
+    assert gpu.shape == cpu.shape, (gpu.shape, cpu.shape)
+    for b in range(2):
+        live_c = cpu[b][cpu[b, :, 3] != 0]
+        live_g = gpu[b][gpu[b, :, 3] != 0]
+        assert live_g.size(0) == int(want_len[b]), \
+            f"item {b}: {live_g.size(0)} events, want {int(want_len[b])}"
+        # signed event count per (bin, y, x) cell
+        cells = []
+        for ev in (live_c, live_g):
+            c = torch.zeros(3, 8, 8, dtype=torch.int64)
+            bins = ((ev[:, 2] - 1e-6) * 3).long().clamp(0, 2)
+            c.index_put_((bins, ev[:, 1].long(), ev[:, 0].long()),
+                         ev[:, 3].long(), accumulate=True)
+            cells.append(c)
+        assert torch.equal(cells[0], stack[b].round().long())
+        assert torch.equal(cells[1], cells[0]), \
+            f"item {b}: {int((cells[1] != cells[0]).sum())} cells differ"
+
+
 def test_redistribute_gpu_sorted_and_padded():
     from esr_amd.ops.events import redistribute_stack
     stack = _rand_stack((2, 3, 8, 8), seed=3).to(DEV)
