@@ -58,6 +58,14 @@ def _deform_conv2d_torch(input, offset, mask, weight, bias,
 
     Matches ESR:models/DCNv2/src/cuda/dcn_v2_im2col_cuda.cu:125-195 including
     zero-padded bilinear sampling outside the image.
+
+    Boundary rule, the HIP kernels' (sample_in_range in deform_conv.hip) and
+    the reference's: a sample at (h, w) counts only where -1 < h < H and
+    -1 < w < W.  The constant mask below changes no value (at h = -1 the
+    only corner inside the image has weight 0), but it fixes the offset
+    gradient: at an integer coordinate it is the one-sided derivative of
+    the cell [floor, floor + 1], and at h <= -1, w <= -1, h >= H or w >= W
+    both components are zero.
     """
     B, C, H, W = input.shape
     Cout, Cin, kh, kw = weight.shape
@@ -86,6 +94,7 @@ def _deform_conv2d_torch(input, offset, mask, weight, bias,
     w0 = w_im.floor()
     lh = h_im - h0
     lw = w_im - w0
+    in_range = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
 
     inp = input.view(B, dg, C // dg, H * W)
     cols = torch.zeros(B, dg, C // dg, K, Ho, Wo, device=dev, dtype=dt)
@@ -94,7 +103,8 @@ def _deform_conv2d_torch(input, offset, mask, weight, bias,
             hc = h0 + dy
             wc = w0 + dx
             valid = (hc >= 0) & (hc < H) & (wc >= 0) & (wc < W)
-            wgt = ((lh if dy else 1 - lh) * (lw if dx else 1 - lw)) * valid
+            wgt = ((lh if dy else 1 - lh) * (lw if dx else 1 - lw)) \
+                * (valid & in_range)
             idx = (hc.clamp(0, H - 1) * W + wc.clamp(0, W - 1)).long()
             idx_f = idx.view(B, dg, 1, K * Ho * Wo).expand(-1, -1, C // dg, -1)
             gathered = torch.gather(inp, 3, idx_f).view(B, dg, C // dg, K, Ho, Wo)

@@ -3,9 +3,10 @@
 Oracle methodology: every native kernel is compared against a
 plain-PyTorch reference computed from the SAME bf16-rounded inputs, so the
 only allowed divergence is fp32 accumulation order + the final bf16
-rounding of the output.  The forward is held to the derived per-element
-bound of tests/bound_rules.py (conv_bound) against a float64 reference;
-the backward and whole-model tests keep the looser _assert_close rule.
+rounding of the output.  The forward (conv_bound) and the backward
+(conv_bwd_bound), native and aten, are held to the derived per-element
+bounds of tests/bound_rules.py against a float64 reference; the
+whole-model tests keep the looser _assert_close rule.
 """
 
 import os
@@ -14,7 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from bound_rules import assert_within, conv_bound, conv_ref64
+from bound_rules import (assert_within, conv_bound, conv_bwd_bound,
+                         conv_bwd_ref64, conv_ref64, count_over)
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +126,47 @@ def test_conv_forward_matches_oracle(cin, cout, h, w, ks, stride, act):
 def test_conv_backward_matches_oracle(cin, cout, h, w, ks, stride, act, bwd,
                                       monkeypatch):
     monkeypatch.setenv("ESR_CONV_BWD", bwd)
-    _backward_vs_oracle(3, cin, cout, h, w, ks, stride, act)
+    loose_dx = bwd == "aten" and \
+        (cin, cout, h, w, ks, stride, act) in MIOPEN_DX_OVER
+    _backward_vs_oracle(3, cin, cout, h, w, ks, stride, act, bwd, loose_dx)
+
+
+# aten cases whose input grad MIOpen (the library's code, not this
+# project's) returns outside conv_bwd_bound; their dx keeps the looser
+# _assert_close rule, dW and db the bound.  Measured on MI355X: 192->64
+# 32x32 k3 s1, act None: 29347 of 589824 dx elements over, worst diff/bound
+# 7.47 (the native dgrad on the same case: 0 over, 0.47).  The cause was
+# not investigated; supposed only: with act None the bound has no u*S term,
+# which an algorithm that rounds an intermediate to bf16 could not meet.
+MIOPEN_DX_OVER = {(192, 64, 32, 32, 3, 1, None)}
+
+
+# native only, chosen from the kernels' tiling: (B, Cin, Cout, H, W, ks,
+# stride, act)
+NATIVE_BWD_EDGES = [
+    # Cin_p 48 = 1.5 ci-blocks, Cout_p 80 = 1.25 co-blocks of
+    # conv2d_wgrad_s1_kernel, uw 2 with an 8-wide last chunk, H 7 = 4 + 3 rows
+    (3, 48, 80, 7, 40, 3, 1, None),
+    # fpb = 2 with an odd batch: the last block holds one frame
+    # (b0 + bf < B)
+    (33, 128, 128, 6, 256, 3, 1, None),
+    # conv2d_wgrad_s1_kernel<1> and the 1x1 dgrad, W one past a chunk
+    (3, 40, 48, 5, 33, 1, 1, "relu"),
+    # conv2d_dgrad_s2 and the stride-2 wgrad at odd H and W: Ho 9 / Wo 18,
+    # the last input row and column are reached by one tap only
+    (3, 32, 64, 17, 35, 3, 2, None),
+    # Ho 17 = 16 + 1 rows: a second, one-row slab of rows_per_blk 16; uw 3
+    (3, 32, 64, 34, 70, 3, 2, None),
+    # Cout one past a tile; dgrad through conv2d_fwd_valu (Cin 16)
+    (3, 16, 33, 20, 44, 3, 1, None),
+]
+
+
+@pytest.mark.parametrize("batch,cin,cout,h,w,ks,stride,act", NATIVE_BWD_EDGES)
+def test_conv_backward_native_tiling_edges(batch, cin, cout, h, w, ks, stride,
+                                           act, monkeypatch):
+    monkeypatch.setenv("ESR_CONV_BWD", "native")
+    _backward_vs_oracle(batch, cin, cout, h, w, ks, stride, act, "native")
 
 
 def test_wgrad_multi_frame_blocks(monkeypatch):
@@ -133,11 +175,20 @@ def test_wgrad_multi_frame_blocks(monkeypatch):
     the rolling X window for the second.  H = 6 leaves a partial 4-row
     chunk."""
     monkeypatch.setenv("ESR_CONV_BWD", "native")
-    _backward_vs_oracle(32, 128, 128, 6, 256, 3, 1, None)
+    _backward_vs_oracle(32, 128, 128, 6, 256, 3, 1, None, "native")
 
 
-def _backward_vs_oracle(batch, cin, cout, h, w, ks, stride, act):
+def _backward_vs_oracle(batch, cin, cout, h, w, ks, stride, act, bwd=None,
+                        loose_dx=False):
+    """dx, dW and db of _NativeConv2dFn under ESR_CONV_BWD = `bwd` (None: as
+    the caller has set it) against float64 conv autograd on the same bf16
+    operands, for the incoming gradient dy * act'(y) on the kernel's own
+    forward output: every element within conv_bwd_bound.  `loose_dx`
+    (MIOPEN_DX_OVER only) holds dx to _assert_close against the same
+    reference instead."""
     from esr_amd.ops.conv import ACT_IDS, _NativeConv2dFn
+    bwd = bwd or os.environ["ESR_CONV_BWD"]
+    assert os.environ["ESR_CONV_BWD"] == bwd
     x = _rand_bf16(batch, cin, h, w, seed=cin * 3 + cout)
     wt = _rand_bf16(cout, cin, ks, ks, seed=cin - cout, scale=0.3)
     b = _rand_bf16(cout, seed=9)
@@ -149,24 +200,23 @@ def _backward_vs_oracle(batch, cin, cout, h, w, ks, stride, act):
     gy = _rand_bf16(*y.shape, seed=31)
     y.backward(gy)
 
-    xr = x.float().clone().requires_grad_(True)
-    wr = wt.float().clone().requires_grad_(True)
-    br = b.float().clone().requires_grad_(True)
-    ref = F.conv2d(xr, wr, br, stride=stride, padding=ks // 2)
-    if act == "relu":
-        ref = F.relu(ref)
-    elif act == "sigmoid":
-        ref = torch.sigmoid(ref)
-    elif act == "tanh":
-        ref = torch.tanh(ref)
-    ref.backward(gy.float())
-
-    _assert_close(xg.grad, xr.grad, rtol=5e-2,
-                  what=f"dgrad {cin}->{cout} k{ks}s{stride}")
-    _assert_close(wg.grad, wr.grad, rtol=5e-2,
-                  what=f"wgrad {cin}->{cout} k{ks}s{stride}")
-    _assert_close(bg.grad, br.grad, rtol=5e-2,
-                  what=f"bgrad {cin}->{cout} k{ks}s{stride}")
+    refs, Ss = conv_bwd_ref64(x, wt, gy, y.detach(), stride, act)
+    n_w = batch * y.shape[2] * y.shape[3]
+    over = {}
+    for name, got, r, S, n in zip(("dx", "dW", "db"),
+                                  (xg.grad, wg.grad, bg.grad), refs, Ss,
+                                  (9 * cout, n_w, n_w)):
+        assert got.dtype == torch.bfloat16, (name, got.dtype)
+        over[name], worst = count_over(
+            got.cpu(), r, conv_bwd_bound(r, S, n, act, torch.bfloat16))
+        print(f"{bwd} B{batch} {cin}->{cout} {h}x{w} k{ks}s{stride} {act} "
+              f"{name}: {over[name]}/{r.numel()} over, "
+              f"max diff/bound {worst:.3f}")
+    if loose_dx:
+        del over["dx"]
+        _assert_close(xg.grad.cpu(), refs[0], rtol=5e-2,
+                      what=f"dgrad {cin}->{cout} k{ks}s{stride}")
+    assert not any(over.values()), f"elements over the bound: {over}"
 
 
 def test_convlayer_native_vs_fallback():

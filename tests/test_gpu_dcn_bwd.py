@@ -2,12 +2,20 @@
 LDS, offset / mask grads in the same pass), the saved im2col columns and
 the path choice, against the CPU fp32 autograd oracle
 (`_deform_conv2d_torch`).  Inputs as tests/test_gpu_kernels.py::_dcn_problem:
-offsets randn * scale, mask rand."""
+offsets randn * scale, mask rand.
+
+The `*_within_bounds` tests hold all five grads, on both paths and in all
+three types, to the per-element float64 bounds of tests/bound_rules.py
+(dcn_bwd_bounds), on offsets drawn from a binary grid so that samples land
+exactly on pixels, on -1 and on H-1 / W-1."""
 
 import functools
 
 import pytest
 import torch
+
+from bound_rules import (count_over, dcn_bwd_bounds, dcn_bwd_ref64,
+                         dcn_grid_problem)
 
 pytestmark = pytest.mark.gpu
 
@@ -127,7 +135,11 @@ def test_whole_group_edge():
 def test_fused_16bit_no_worse_than_split(dtype):
     """Both paths keep an fp32 sum and round once, so only the add order
     differs: per grad the fused max-abs error against the fp32 oracle (on
-    the same 16-bit-rounded inputs) is at most 2x the split path's."""
+    the same 16-bit-rounded inputs) is at most 2x the split path's.
+    Beside it both paths are held to the float64 bounds, so they cannot be
+    wrong in the same way; that problem has grid offsets and 30 rows, not
+    32: the weight grad sums B*Ho*Wo + 8 terms in fp32 and the bound rule
+    wants that below 2^11."""
     tensors, ref = _problem(2, 16, 32, 32, 16, 4, seed=11, dtype=dtype)
     fused = _run(tensors, 4, "fused", dtype=dtype)
     split = _run(tensors, 4, "split", dtype=dtype)
@@ -139,6 +151,12 @@ def test_fused_16bit_no_worse_than_split(dtype):
     print(f"DCN backward max-abs errors ({dtype}) -", report)
     bad = [n for n, a, b in zip(NAMES, ef, es) if not a <= 2 * b]
     assert not bad, f"fused worse than 2x split on {bad} - {report}"
+
+    tensors, ref, bounds = _bound_problem(2, 16, 30, 32, 16, 4, seed=11,
+                                          dtype=dtype)
+    for path in ("fused", "split"):
+        _check_bounds(_run(tensors, 4, path, dtype=dtype), ref, bounds,
+                      dtype, f"30x32 {path}")
 
 
 def test_fused_run_to_run():
@@ -206,3 +224,138 @@ def test_graph_capture_replays():
             assert torch.isfinite(got).all()
             assert torch.allclose(got.float(), want.float(),
                                   atol=ATOL, rtol=RTOL)
+
+
+# ------------------------------------------- per-element float64 bounds
+DTYPES = [torch.float32, torch.bfloat16, torch.float16]
+DT_IDS = ["fp32", "bf16", "fp16"]
+PATHS = ["fused", "split"]
+
+
+@functools.lru_cache(maxsize=None)
+def _bound_problem(B, C, H, W, Cout, dg, stride=1, pad=1, dil=1,
+                   off_scale=2.0, seed=0, dtype=torch.float32, lattice=None):
+    """Grid-offset CPU tensors (input, offset, mask, weight, bias, grad_out)
+    rounded to `dtype`, the float64 grads and their bounds.  Cached: callers
+    must not modify what they get."""
+    args, gout = dcn_grid_problem(B, C, H, W, Cout, dg, stride, pad, dil,
+                                  off_scale, seed, dtype, lattice)
+    geom = (stride, pad, dil, dg)
+    ref = dcn_bwd_ref64(args, gout, geom)
+    return args + [gout], ref, dcn_bwd_bounds(args, gout, geom, ref, dtype)
+
+
+def _check_bounds(grads, ref, bounds, dtype, what):
+    """All five grads, every element counted; prints each worst diff/bound
+    before asserting."""
+    over = {}
+    for n, g, r, bd in zip(NAMES, grads, ref, bounds):
+        assert g.dtype == dtype, (n, g.dtype)
+        over[n], worst = count_over(g.cpu(), r, bd)
+        print(f"{what} {str(dtype)[6:]} grad_{n}: {over[n]}/{r.numel()} "
+              f"over, "
+              f"max diff/bound {worst:.3f}")
+    assert not any(over.values()), f"{what}: elements over the bound {over}"
+
+
+def _run_counted(tensors, dg, path, **kw):
+    """_run, and check that `path` is the one that ran."""
+    from esr_amd.ops import dcn
+    other = "split" if path == "fused" else "fused"
+    before = dict(dcn.stats)
+    grads = _run(tensors, dg, path, **kw)
+    assert dcn.stats["bwd_" + path] == before["bwd_" + path] + 1
+    assert dcn.stats["bwd_" + other] == before["bwd_" + other]
+    return grads
+
+
+@pytest.mark.parametrize("off_scale", [2.0, 8.0])
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+def test_main_shape_within_bounds(dtype, path, off_scale):
+    """B2 C16 14x18 Cout12 dg4: partial waves, two x-tiles of the tiled
+    col2im with the second partial.  On the split path fp32 takes
+    dcn_col2im_tiled_kernel and the 16-bit types dcn_col2im_kernel
+    (ESR_DCN_TILED is read once per process and left alone here).  Scale 8
+    pushes samples beyond the tile's +-4 halo, so the tiled kernel's
+    global-atomic fallback runs, and many outside the image."""
+    tensors, ref, bounds = _bound_problem(2, 16, 14, 18, 12, 4,
+                                          off_scale=off_scale, seed=3,
+                                          dtype=dtype)
+    grads = _run_counted(tensors, 4, path, dtype=dtype)
+    _check_bounds(grads, ref, bounds, dtype, f"14x18 s{off_scale:g} {path}")
+
+
+def test_tiled_grid_within_bounds():
+    """18x34 in fp32 on the split path: 2x3 tiles of dcn_col2im_tiled_kernel,
+    partial in both directions."""
+    tensors, ref, bounds = _bound_problem(1, 8, 18, 34, 4, 2, off_scale=2.0,
+                                          seed=17)
+    grads = _run_counted(tensors, 2, "split")
+    _check_bounds(grads, ref, bounds, torch.float32, "18x34 split")
+
+
+@pytest.mark.parametrize("lattice", ["zero", "int"])
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("dtype", DTYPES[:2], ids=DT_IDS[:2])
+def test_lattice_offsets_within_bounds(dtype, path, lattice):
+    """All-zero offsets (DeformAlign2d's initial state: every top-row and
+    left-column tap exactly on -1) and integer offsets in {-2..2}: every
+    sample sits on a pixel, where the offset grad is the one-sided
+    derivative of the cell [floor, floor + 1], and zero at <= -1."""
+    tensors, ref, bounds = _bound_problem(2, 16, 14, 18, 12, 4, seed=19,
+                                          dtype=dtype, lattice=lattice)
+    grads = _run_counted(tensors, 4, path, dtype=dtype)
+    _check_bounds(grads, ref, bounds, dtype, f"lattice {lattice} {path}")
+
+
+@pytest.mark.parametrize("C,dg,Cout", [(12, 2, 5), (16, 8, 5)],
+                         ids=["cpg6", "cpg2"])
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("dtype", DTYPES[:2], ids=DT_IDS[:2])
+def test_cpg_tail_within_bounds(dtype, path, C, dg, Cout):
+    """cpg 6 and 2 against the fused kernel's four-channel chunks, and the
+    same through the split kernels."""
+    tensors, ref, bounds = _bound_problem(1, C, 9, 11, Cout, dg, seed=13,
+                                          dtype=dtype)
+    grads = _run_counted(tensors, dg, path, dtype=dtype)
+    _check_bounds(grads, ref, bounds, dtype, f"9x11 cpg{C // dg} {path}")
+
+
+@pytest.mark.parametrize("stride,pad,dil", [(2, 1, 1), (1, 2, 2)])
+@pytest.mark.parametrize("path", PATHS)
+@pytest.mark.parametrize("dtype", DTYPES[:2], ids=DT_IDS[:2])
+def test_stride_and_dilation_within_bounds(dtype, path, stride, pad, dil):
+    tensors, ref, bounds = _bound_problem(1, 8, 16, 16, 4, 2, stride=stride,
+                                          pad=pad, dil=dil, off_scale=1.0,
+                                          seed=9, dtype=dtype)
+    grads = _run_counted(tensors, 2, path, stride=stride, pad=pad, dil=dil,
+                         dtype=dtype)
+    _check_bounds(grads, ref, bounds, dtype,
+                  f"16x16 s{stride}p{pad}d{dil} {path}")
+
+
+@pytest.mark.parametrize("save", [None, "0"], ids=["saved", "rebuilt"])
+def test_autograd_bf16_within_bounds(monkeypatch, save):
+    """Grads through modulated_deform_conv2d in bf16, with the forward's
+    columns saved (ESR_DCN_SAVE_COLS unset) and rebuilt in the backward."""
+    from esr_amd.ops import dcn
+    if save is None:
+        monkeypatch.delenv("ESR_DCN_SAVE_COLS", raising=False)
+    else:
+        monkeypatch.setenv("ESR_DCN_SAVE_COLS", save)
+    monkeypatch.delenv("ESR_DCN_BWD", raising=False)
+    dtype = torch.bfloat16
+    tensors, ref, bounds = _bound_problem(2, 16, 14, 18, 12, 4, seed=3,
+                                          dtype=dtype)
+    *args, gout = [t.to("cuda", dtype) for t in tensors]
+    leaves = [t.clone().requires_grad_(True) for t in args]
+    before = dict(dcn.stats)
+    out = dcn.modulated_deform_conv2d(*leaves, stride=1, padding=1,
+                                      dilation=1, deformable_groups=4)
+    out.backward(gout)
+    assert dcn.stats["bwd_fused"] == before["bwd_fused"] + 1
+    assert dcn.stats["bwd_cols_saved"] == \
+        before["bwd_cols_saved"] + (save is None)
+    _check_bounds([t.grad for t in leaves], ref, bounds, dtype,
+                  f"autograd cols {'saved' if save is None else 'rebuilt'}")

@@ -167,8 +167,8 @@ def test_dcn_split_kernels_wrap():
 
 
 def test_conv2d_dgrad_s2_wraps(monkeypatch):
-    """32 -> 64 3x3 stride 2 through the all-native backward; the existing
-    backward rule."""
+    """32 -> 64 3x3 stride 2 through the all-native backward; dx, dW and db
+    within conv_bwd_bound of tests/bound_rules.py (test_gpu_conv's rule)."""
     h = _scaled(74)
     _assert_wraps(3 * 32 * h * 74, "conv2d_dgrad_s2 items")
     monkeypatch.setenv("ESR_CONV_BWD", "native")
