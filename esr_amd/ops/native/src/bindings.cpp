@@ -83,6 +83,10 @@ void evs_batch_splat(const at::Tensor&, const at::Tensor&, at::Tensor&,
                      int64_t, int64_t, int64_t);
 int64_t evs_batch_splat_chunk();
 
+// eval_metrics.hip
+at::Tensor restoration_metrics(const at::Tensor&, const at::Tensor&, double);
+std::vector<int64_t> restoration_metrics_tile();
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
         "modulated deformable conv forward (gfx950)");
@@ -138,5 +142,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "tensor) into [J,2,kH,kW] count planes, in place");
   m.def("evs_batch_splat_chunk", &evs_batch_splat_chunk,
         "events one block of evs_batch_splat covers");
+  m.def("restoration_metrics", &restoration_metrics,
+        "per-plane sum|p-t|, sum(p-t)^2, max t, min t and 7x7 SSIM sum of "
+        "fp32 [P,H,W] maps, fp64 [P,5], deterministic");
+  m.def("restoration_metrics_tile", &restoration_metrics_tile,
+        "(TH, TW) pixel tile one block of restoration_metrics owns");
   m.attr("gfx_arch") = "gfx950";
 }

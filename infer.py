@@ -10,6 +10,7 @@ import yaml
 
 from esr_amd.data import read_datalist
 from esr_amd.engine import load_model_from_checkpoint
+from esr_amd.engine.device_inference import infer_sequence_device
 from esr_amd.engine.inference import build_metrics, infer_sequence
 
 
@@ -60,6 +61,13 @@ def main():
     p.add_argument("--real_world_test", action="store_true")
     p.add_argument("--no_images", action="store_true")
     p.add_argument("--num_workers", type=int, default=2)
+    p.add_argument("--device_resident", action="store_true",
+                   help="evaluate on the device (engine/device_inference.py):"
+                        " events resident, one graph replay per window, "
+                        "metrics from the fused kernel; needs --no_images")
+    p.add_argument("--amp", choices=["none", "bf16", "fp16"], default="none",
+                   help="autocast dtype of the --device_resident forward; "
+                        "none keeps the harness's fp32 forward")
     p.add_argument("--lpips_weights", type=str, default=None,
                    help="linear-head state dict (defaults to the bundled "
                         "reference v0.1 heads)")
@@ -67,6 +75,16 @@ def main():
                    help="torchvision alexnet/vgg16 checkpoint for "
                         "paper-comparable LPIPS")
     args = p.parse_args()
+
+    if args.device_resident and not args.no_images:
+        raise SystemExit(
+            "--device_resident needs --no_images: the device path renders no "
+            "PNGs (they stay with the default CPU-fed harness)")
+    if args.amp != "none" and not args.device_resident:
+        raise SystemExit("--amp applies to --device_resident only; the "
+                         "default harness runs the fp32 forward")
+    amp_dtype = {"none": None, "bf16": torch.bfloat16,
+                 "fp16": torch.float16}[args.amp]
 
     device = torch.device(args.device if torch.cuda.is_available() else "cpu")
     dl_cfg = default_dataloader_config(args)
@@ -97,9 +115,14 @@ def main():
         all_results = {}
         for path in paths:
             name = Path(path).stem
-            res = infer_sequence(dl_cfg, path, model, device,
-                                 output_path=mdir / name, metrics=metrics,
-                                 save_images=not args.no_images)
+            if args.device_resident:
+                res = infer_sequence_device(
+                    dl_cfg, path, model, device, output_path=mdir / name,
+                    metrics=metrics, save_images=False, amp_dtype=amp_dtype)
+            else:
+                res = infer_sequence(dl_cfg, path, model, device,
+                                     output_path=mdir / name, metrics=metrics,
+                                     save_images=not args.no_images)
             all_results[name] = res
             print(f"{Path(model_path).stem} / {name}: {res}")
 
