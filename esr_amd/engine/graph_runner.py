@@ -16,6 +16,9 @@ With FlatAdam/FlatAdamW (esr_amd/optim) the optimizer's own flat gradient is
 the all-reduced buffer, the backward runs on ``optimizer.scale_loss(loss)``
 and the overflow skip / scale update are device-side parts of the captured
 step; the learning rate is a device scalar refreshed before each replay.
+Gradient-norm clipping is part of FlatAdam's step too; for any other
+optimizer `max_grad_norm` clips the flat gradient with three torch ops
+inside the captured step (step.py: `clip_flat_grad_`).
 
 The step body itself is step.py's, shared with the eager trainer; the
 warm-up / roll-back / capture sequence is capture.py's `capture_graph`, and
@@ -56,7 +59,8 @@ class GraphedBPTTStep:
     def __init__(self, model, optimizer, flat_grad, n_windows,
                  inp_shape, gt_shape, device, amp_dtype=None,
                  world_size: int = 1, warmup: int = 3,
-                 sequence: bool = False, seqn: int = 3):
+                 sequence: bool = False, seqn: int = 3,
+                 max_grad_norm=None):
         self.model = model
         self.optimizer = optimizer
         self.flat_grad = flat_grad
@@ -65,6 +69,9 @@ class GraphedBPTTStep:
         self.world = world_size
         self.sequence = sequence
         self.seqn = seqn
+        # only for optimizers that do not clip on their own
+        self.max_grad_norm = max_grad_norm
+        self.static_grad_norm = None
         # sequence: one inp_shape = [B, L, C, H, W] frames tensor and one
         # gt_shape = [B, n_windows, C, H, W]; otherwise one pair per window
         n_bufs = 1 if sequence else n_windows
@@ -90,7 +97,10 @@ class GraphedBPTTStep:
             autocast=amp_autocast(self.amp_dtype, self.device,
                                   cache_enabled=False),
             loss_fn=F.mse_loss)
-        backward_and_step(loss, self.optimizer, self._all_reduce)
+        # the last assignment is the capture's: the replays' static output
+        self.static_grad_norm = backward_and_step(
+            loss, self.optimizer, self._all_reduce,
+            max_grad_norm=self.max_grad_norm, flat_grad=self.flat_grad)
         return loss, mse
 
     def capture(self):

@@ -15,7 +15,11 @@ MI355X deltas:
   * optional dynamic loss scaling (top-level ``loss_scale`` key) for fp16
     autocast: device-side inside FlatAdam/FlatAdamW (capture-safe, works
     under hip_graphs), torch.amp.GradScaler for any other optimizer in
-    eager mode.
+    eager mode;
+  * optional gradient-norm clipping (top-level ``grad_clip`` key): inside
+    FlatAdam/FlatAdamW's device-side step, ``clip_grad_norm_`` (eager) or
+    three torch ops on the flat gradient (hip_graphs) for any other
+    optimizer; always on the synchronized, un-scaled gradient.
 """
 
 from __future__ import annotations
@@ -26,14 +30,14 @@ import torch
 
 from ..config import build_lr_scheduler, build_optimizer
 from ..config.parser import FLAT_OPTIMIZERS
-from ..optim import flat_grad_of, loss_scale_stats
+from ..optim import flat_grad_of, grad_clip_stats, loss_scale_stats
 from ..parallel import get_rank, reduce_tensor
 from ..utils import MetricTracker, MetricWriter
 from .capture import amp_autocast
 from .checkpoint import Resumer, save_checkpoint
 from .step import backward_and_step, bptt_loss
 
-__all__ = ["Trainer", "loss_scale_plan"]
+__all__ = ["Trainer", "loss_scale_plan", "grad_clip_plan"]
 
 
 def loss_scale_plan(cfg: dict, use_graphs: bool):
@@ -66,11 +70,37 @@ def loss_scale_plan(cfg: dict, use_graphs: bool):
     return "grad_scaler", settings
 
 
+def grad_clip_plan(cfg: dict):
+    """Decide who clips the gradient norm for this config.
+
+    Returns ``(mode, max_norm)``: ``("off", None)`` when the top-level
+    ``grad_clip`` key is absent or disabled, ``("flat", max_norm)`` when the
+    optimizer is FlatAdam/FlatAdamW (inside its device-side step) and
+    ``("torch", max_norm)`` for any other optimizer (torch ops in the step).
+    """
+    gc = cfg.get("grad_clip") or {}
+    unknown = set(gc) - {"enabled", "max_norm"}
+    if unknown:
+        raise ValueError(f"unknown grad_clip keys {sorted(unknown)}; "
+                         f"known: ['enabled', 'max_norm']")
+    if not gc.get("enabled", False):
+        return "off", None
+    if "max_norm" not in gc:
+        raise ValueError("grad_clip needs a max_norm")
+    max_norm = gc["max_norm"]
+    if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) \
+            or not (math.isfinite(max_norm) and max_norm > 0):
+        raise ValueError(f"grad_clip.max_norm must be a positive finite "
+                         f"number, got {max_norm!r}")
+    flat = cfg["optimizer"]["name"] in FLAT_OPTIMIZERS
+    return ("flat" if flat else "torch"), float(max_norm)
+
+
 class Trainer:
     def __init__(self, config_parser, train_dataloader, valid_dataloader,
                  model, loss_fns, optimizer, lr_scheduler, logger, device,
                  resume: str | None = None, reset: bool = False,
-                 grad_scaler=None):
+                 grad_scaler=None, max_grad_norm=None):
         self.config_parser = config_parser
         self.cfg = config_parser.config
         self.train_dataloader = train_dataloader
@@ -83,6 +113,10 @@ class Trainer:
         self.device = device
         # torch.amp.GradScaler for the eager non-Flat loss-scaling case
         self.grad_scaler = grad_scaler
+        # clipping done in the step for optimizers that do not clip on
+        # their own (grad_clip_plan's "torch" mode), and its last norm
+        self.max_grad_norm = max_grad_norm
+        self._torch_grad_norm = None
         self.amp_dtype = {"bf16": torch.bfloat16, "fp16": torch.float16,
                           None: None, "fp32": None}[
                               self.cfg.get("precision", None)]
@@ -178,7 +212,8 @@ class Trainer:
             self.model, self.optimizer, flat, n_windows,
             inp_shape, gt_shape, self.device,
             amp_dtype=self.amp_dtype, world_size=get_world_size(),
-            sequence=shared, seqn=self.train_dataloader.seqn).capture()
+            sequence=shared, seqn=self.train_dataloader.seqn,
+            max_grad_norm=self.max_grad_norm).capture()
         self._graph_step = (key, runner)
         return runner
 
@@ -191,6 +226,7 @@ class Trainer:
             loss, mse = runner.run(
                 [w["inp_scaled_cnt"] for w in inputs_seq],
                 [w["gt_cnt"][:, self.mid_idx] for w in inputs_seq])
+        self._torch_grad_norm = runner.static_grad_norm
         return loss.detach().clone(), mse.detach().clone(), None
 
     def bptt_step(self, inputs_seq, train: bool = True):
@@ -231,8 +267,9 @@ class Trainer:
             autocast=amp_autocast(self.amp_dtype, self.device),
             loss_fn=self.loss_fns["mse"])
         if train:
-            backward_and_step(loss, self.optimizer,
-                              self._sync_grads_if_needed, self.grad_scaler)
+            self._torch_grad_norm = backward_and_step(
+                loss, self.optimizer, self._sync_grads_if_needed,
+                self.grad_scaler, max_grad_norm=self.max_grad_norm)
         return loss.detach(), mse_loss.detach(), pred.detach()
 
     def _sync_grads_if_needed(self):
@@ -306,7 +343,8 @@ class Trainer:
                            lr=None):
         """Reduce the step's losses over the ranks; on rank 0 feed the
         metrics (and the `lr` scalar, if given) at writer step `step` and,
-        when `log`, write ``message(mse, loss)`` and the loss scale."""
+        when `log`, write ``message(mse, loss)``, the loss scale and the
+        gradient norm."""
         reduced_mse = reduce_tensor(mse_loss)
         reduced_loss = reduce_tensor(loss)
         if get_rank() != 0:
@@ -320,6 +358,7 @@ class Trainer:
         if log:
             self.logger.info(message(reduced_mse, reduced_loss))
             self._log_loss_scale()
+            self._log_grad_clip()
 
     def iteration_based_training(self):
         self.model.train()
@@ -425,6 +464,27 @@ class Trainer:
         if skipped is not None:
             self.writer.add_scalar("skipped_steps", skipped)
             msg += f" skipped_steps {skipped}"
+        self.logger.info(msg)
+
+    def grad_clip_stats(self):
+        """(un-scaled gradient norm of the last step, clipped steps or None)
+        or None when clipping is off.  Reading synchronizes with the
+        device: call at logging cadence only."""
+        stats = grad_clip_stats(self.optimizer)
+        if stats is None and self._torch_grad_norm is not None:
+            stats = float(self._torch_grad_norm), None
+        return stats
+
+    def _log_grad_clip(self):
+        stats = self.grad_clip_stats()
+        if stats is None:
+            return
+        norm, clipped = stats
+        self.writer.add_scalar("grad_norm", norm)
+        msg = f"grad_norm {norm:.4e}"
+        if clipped is not None:
+            self.writer.add_scalar("clipped_steps", clipped)
+            msg += f" clipped_steps {clipped}"
         self.logger.info(msg)
 
     def _valid(self, stamp):
@@ -570,6 +630,7 @@ def build_training(config_parser, device, logger, resume=None, reset=False):
     opt_name = cfg["optimizer"]["name"]
     flat_opt = opt_name in FLAT_OPTIMIZERS
     ls_mode, ls_settings = loss_scale_plan(cfg, use_graphs)
+    gc_mode, max_grad_norm = grad_clip_plan(cfg)
     if use_graphs:
         # graphed mode does its own single-bucket RCCL all-reduce inside the
         # captured step; DDP's hook-driven reducer is not used
@@ -592,6 +653,8 @@ def build_training(config_parser, device, logger, resume=None, reset=False):
         opt_kwargs["capturable"] = True
     if ls_mode == "flat":
         opt_kwargs["loss_scale"] = ls_settings
+    if gc_mode == "flat":
+        opt_kwargs["max_grad_norm"] = max_grad_norm
     optimizer = build_optimizer(opt_name, params, **opt_kwargs)
     grad_scaler = None
     if ls_mode == "grad_scaler":
@@ -600,4 +663,6 @@ def build_training(config_parser, device, logger, resume=None, reset=False):
                                       **cfg["lr_scheduler"]["args"])
     return Trainer(config_parser, train_loader, valid_loader, model, loss_fns,
                    optimizer, lr_scheduler, logger, device,
-                   resume=resume, reset=reset, grad_scaler=grad_scaler)
+                   resume=resume, reset=reset, grad_scaler=grad_scaler,
+                   max_grad_norm=max_grad_norm if gc_mode == "torch"
+                   else None)

@@ -72,6 +72,12 @@ void flat_adam_step(at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
                     double, double, double, double, bool);
 void flat_scale_update(at::Tensor&, bool, double, double, int64_t, double,
                        double);
+void flat_grad_stats(const at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+                     double);
+void flat_adam_step_clipped(at::Tensor&, const at::Tensor&, at::Tensor&,
+                            at::Tensor&, const c10::optional<at::Tensor>&,
+                            const at::Tensor&, const at::Tensor&, double,
+                            double, double, double, bool);
 
 // stream_ingest.hip
 void stream_window_advance(at::Tensor&, const at::Tensor&);
@@ -131,6 +137,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flat-buffer Adam/AdamW step with device-side un-scale and skip");
   m.def("flat_scale_update", &flat_scale_update,
         "GradScaler-style scale/step update of the device state");
+  m.def("flat_grad_stats", &flat_grad_stats,
+        "finite check plus deterministic fp64 sum of squares of the flat "
+        "grad; writes grad norm, clip coefficient and clipped-step count");
+  m.def("flat_adam_step_clipped", &flat_adam_step_clipped,
+        "flat_adam_step with the gradient multiplied by the clip "
+        "coefficient after un-scaling");
   m.def("stream_window_advance", &stream_window_advance,
         "per-stream sliding-window shift/reset of a [seqn,S,2,kH,kW] buffer, "
         "control read from a device tensor");

@@ -10,7 +10,8 @@ import torch
 from .flat_adam import LOSS_SCALE_DEFAULTS, FlatAdam, FlatAdamW
 
 __all__ = ["FlatAdam", "FlatAdamW", "LOSS_SCALE_DEFAULTS", "flat_grad_of",
-           "scale_loss", "sync_lr", "loss_scale_stats", "snapshot_optimizer",
+           "scale_loss", "sync_lr", "loss_scale_stats", "grad_clip_stats",
+           "snapshot_optimizer",
            "restore_optimizer"]
 
 
@@ -44,6 +45,16 @@ def loss_scale_stats(opt, grad_scaler=None):
     if grad_scaler is not None:
         return grad_scaler.get_scale(), None
     return None
+
+
+def grad_clip_stats(opt):
+    """(un-scaled gradient norm of the last step, clipped steps) from
+    ``opt.max_grad_norm`` with ``grad_norm_value`` / ``clipped_steps``; None
+    when the optimizer does not clip.  Reading synchronizes with the
+    device."""
+    if getattr(opt, "max_grad_norm", None) is None:
+        return None
+    return opt.grad_norm_value, opt.clipped_steps
 
 
 def _state_tensors(opt):

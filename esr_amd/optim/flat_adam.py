@@ -10,10 +10,18 @@ independent of the number of parameter tensors:
     flat_adam_step           un-scale + Adam/AdamW, no-op on overflow
     flat_scale_update        GradScaler scale/tracker + step counter
 
-The skip decision, the loss scale, the step count and the learning rate are
-device scalars, so the whole step records into a hipGraph and a replay
-honours ``param_groups[0]['lr']`` changes made by an lr scheduler (the host
-writes the device scalar outside the captured region, see ``sync_lr``).
+With ``max_grad_norm`` the gradient's global L2 norm is clipped as
+``torch.nn.utils.clip_grad_norm_`` would, on the un-scaled gradient and
+inside the same phase (four launches): ``flat_grad_stats`` replaces the
+finite check (it does both jobs in one pass over the gradient and then
+finishes the norm in one block), and the step kernel multiplies by the
+coefficient.
+
+The skip decision, the loss scale, the clip coefficient, the step count and
+the learning rate are device scalars, so the whole step records into a
+hipGraph and a replay honours ``param_groups[0]['lr']`` changes made by an
+lr scheduler (the host writes the device scalar outside the captured region,
+see ``sync_lr``).
 
 On CPU tensors ``step()`` runs a pure-torch implementation of the same
 semantics (the CPU oracle, as elsewhere in ``ops/``).  On GPU tensors the
@@ -31,7 +39,8 @@ import math
 import torch
 from torch.optim import Optimizer
 
-__all__ = ["FlatAdam", "FlatAdamW", "LOSS_SCALE_DEFAULTS", "STATE_SIZE"]
+__all__ = ["FlatAdam", "FlatAdamW", "LOSS_SCALE_DEFAULTS", "STATE_SIZE",
+           "CLIP_SIZE"]
 
 # torch.amp.GradScaler's defaults
 LOSS_SCALE_DEFAULTS = {"init_scale": 65536.0, "growth_factor": 2.0,
@@ -40,6 +49,12 @@ LOSS_SCALE_DEFAULTS = {"init_scale": 65536.0, "growth_factor": 2.0,
 # device state layout (fp32; must match flat_adam.hip)
 SCALE, TRACKER, FOUND_INF, STEP, LR, SKIPPED, BC1, BC2_SQRT = range(8)
 STATE_SIZE = 8
+# clip scalars, a tensor of their own (fp32; must match flat_adam.hip)
+GRAD_NORM, CLIP_COEF, CLIPPED = range(3)
+CLIP_SIZE = 3
+# launch geometry of the flat kernels (esr_common.h): 256 threads x float4,
+# at most 2048 blocks; the stats pass leaves one fp64 partial per block
+_ELEMS_PER_BLOCK, _MAX_BLOCKS = 1024, 2048
 
 _HYPER_KEYS = ("lr", "betas", "eps", "weight_decay", "amsgrad",
                "decoupled_weight_decay")
@@ -77,11 +92,22 @@ class FlatAdam(Optimizer):
     ``loss_scale`` is None (off) or a dict with any of ``init_scale``,
     ``growth_factor``, ``backoff_factor``, ``growth_interval``.
     One set of hyper-parameters applies to all params.
+
+    ``max_grad_norm`` is None (off) or the L2 norm the un-scaled gradient is
+    clipped to before each step (``clip_grad_norm_``'s formula; weight decay
+    is added after clipping).  It is fixed at construction and baked into a
+    captured graph.  With clipping on, a non-finite gradient skips the step
+    whether or not the loss is scaled.
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, amsgrad=False, decoupled=False,
-                 loss_scale=None):
+                 loss_scale=None, max_grad_norm=None):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
+                raise ValueError(f"max_grad_norm must be positive and "
+                                 f"finite, got {max_grad_norm}")
         if lr < 0 or eps < 0 or weight_decay < 0 \
                 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
             raise ValueError("invalid FlatAdam hyper-parameters")
@@ -129,6 +155,15 @@ class FlatAdam(Optimizer):
 
         self._state = torch.zeros(STATE_SIZE, device=device,
                                   dtype=torch.float32)
+        self._max_norm = max_grad_norm
+        self._clip = self._partials = None
+        if max_grad_norm is not None:
+            self._clip = torch.zeros(CLIP_SIZE, device=device,
+                                     dtype=torch.float32)
+            if device.type == "cuda":  # scratch of the stats pass
+                blocks = min(-(-total // _ELEMS_PER_BLOCK), _MAX_BLOCKS)
+                self._partials = torch.zeros(max(blocks, 1), device=device,
+                                             dtype=torch.float64)
         self._lr_written = None
         self._write_state(scale=self._ls["init_scale"] if self._ls else 1.0,
                           tracker=0, step=0, skipped=0)
@@ -177,11 +212,25 @@ class FlatAdam(Optimizer):
 
     def state_buffers(self):
         """Every tensor a step writes besides the parameters: the device
-        scalars and the moments (esr_amd.optim.snapshot_optimizer)."""
+        scalars, the moments and, with clipping, the clip scalars
+        (esr_amd.optim.snapshot_optimizer)."""
         bufs = [self._state, self.exp_avg, self.exp_avg_sq]
         if self.max_exp_avg_sq is not None:
             bufs.append(self.max_exp_avg_sq)
+        if self._clip is not None:
+            bufs.append(self._clip)
         return bufs
+
+    @property
+    def max_grad_norm(self):
+        """The clipping threshold, None when clipping is off."""
+        return self._max_norm
+
+    @property
+    def clip_state(self):
+        """The fp32 clip scalars (grad norm, clip coefficient, clipped
+        steps) on the device; None when clipping is off."""
+        return self._clip
 
     # reading these synchronizes: logging cadence only
     @property
@@ -199,6 +248,20 @@ class FlatAdam(Optimizer):
     @property
     def growth_tracker(self) -> int:
         return int(self._state[TRACKER])
+
+    # the clip scalars; None when clipping is off
+    @property
+    def grad_norm_value(self):
+        """Un-scaled L2 norm of the last step's gradient."""
+        return None if self._clip is None else float(self._clip[GRAD_NORM])
+
+    @property
+    def clip_coef_value(self):
+        return None if self._clip is None else float(self._clip[CLIP_COEF])
+
+    @property
+    def clipped_steps(self):
+        return None if self._clip is None else int(self._clip[CLIPPED])
 
     def scale_loss(self, loss):
         """loss * scale as a device-scalar multiply (capture-safe); the loss
@@ -243,12 +306,23 @@ class FlatAdam(Optimizer):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
         ls = self._ls
-        if ls is not None:
-            ext.flat_grad_finite_check(self.flat_grad, self._state)
-        ext.flat_adam_step(self.flat_param, self.flat_grad, self.exp_avg,
-                           self.exp_avg_sq, self.max_exp_avg_sq, self._state,
-                           b1, b2, g["eps"], g["weight_decay"],
-                           g["decoupled_weight_decay"])
+        if self._clip is not None:
+            # finite check and norm in one pass, with or without scaling
+            ext.flat_grad_stats(self.flat_grad, self._state, self._partials,
+                                self._clip, self._max_norm)
+            ext.flat_adam_step_clipped(
+                self.flat_param, self.flat_grad, self.exp_avg,
+                self.exp_avg_sq, self.max_exp_avg_sq, self._state,
+                self._clip, b1, b2, g["eps"], g["weight_decay"],
+                g["decoupled_weight_decay"])
+        else:
+            if ls is not None:
+                ext.flat_grad_finite_check(self.flat_grad, self._state)
+            ext.flat_adam_step(self.flat_param, self.flat_grad, self.exp_avg,
+                               self.exp_avg_sq, self.max_exp_avg_sq,
+                               self._state, b1, b2, g["eps"],
+                               g["weight_decay"],
+                               g["decoupled_weight_decay"])
         ext.flat_scale_update(
             self._state, ls is not None,
             ls["growth_factor"] if ls else 1.0,
@@ -256,24 +330,37 @@ class FlatAdam(Optimizer):
             ls["growth_interval"] if ls else 1, b1, b2)
 
     def _step_torch(self):
-        """Same semantics as the three kernels in plain torch ops (fp32,
-        same operation order)."""
+        """Same semantics as the kernels in plain torch ops (fp32, same
+        operation order; the norm in fp64)."""
         st = self._state
         g0 = self.param_groups[0]
         b1, b2 = g0["betas"]
         f32 = lambda x: torch.tensor(x, dtype=torch.float32,  # noqa: E731
                                      device=st.device)
         ls = self._ls
-        found = ls is not None and \
+        clip = self._clip
+        found = (ls is not None or clip is not None) and \
             not bool(torch.isfinite(self.flat_grad).all())
+        if clip is not None:
+            total = float(self.flat_grad.double().square().sum())
+            norm = math.sqrt(total) / float(st[SCALE])
+            coef = self._max_norm / (norm + 1e-6)
+            clips = coef < 1.0  # False for a NaN norm
+            clip[GRAD_NORM] = f32(norm)
+            clip[CLIP_COEF] = f32(coef) if clips else 1.0
+            if clips and not found:
+                clip[CLIPPED] += 1.0
         if found:
-            st[SCALE] *= f32(ls["backoff_factor"])
+            if ls is not None:
+                st[SCALE] *= f32(ls["backoff_factor"])
             st[TRACKER] = 0.0
             st[SKIPPED] += 1.0
             return
         p, m, v = self.flat_param, self.exp_avg, self.exp_avg_sq
         lr = st[LR]
         grad = self.flat_grad * (1.0 / st[SCALE])
+        if clip is not None:  # a second multiply: un-scaling stays exact
+            grad = grad * clip[CLIP_COEF]
         wd = g0["weight_decay"]
         if wd != 0:
             if g0["decoupled_weight_decay"]:
@@ -308,7 +395,8 @@ class FlatAdam(Optimizer):
     def state_dict(self):
         """torch.optim.Adam's layout (per-param step / exp_avg / exp_avg_sq
         [/ max_exp_avg_sq] + param_groups), so checkpoints interchange with
-        Adam/AdamW, plus a top-level ``loss_scale`` entry."""
+        Adam/AdamW, plus a top-level ``loss_scale`` entry and, with
+        clipping on, a top-level ``grad_clip`` entry."""
         st = self._state.detach().cpu()
         step = float(st[STEP])
         state = {}
@@ -328,11 +416,15 @@ class FlatAdam(Optimizer):
             packed["params"] = list(range(start, start + len(g["params"])))
             start += len(g["params"])
             groups.append(packed)
-        return {"state": state, "param_groups": groups,
-                "loss_scale": {"enabled": self._ls is not None,
-                               "scale": float(st[SCALE]),
-                               "growth_tracker": int(st[TRACKER]),
-                               "skipped_steps": int(st[SKIPPED])}}
+        out = {"state": state, "param_groups": groups,
+               "loss_scale": {"enabled": self._ls is not None,
+                              "scale": float(st[SCALE]),
+                              "growth_tracker": int(st[TRACKER]),
+                              "skipped_steps": int(st[SKIPPED])}}
+        if self._clip is not None:
+            out["grad_clip"] = {"max_norm": self._max_norm,
+                                "clipped_steps": self.clipped_steps}
+        return out
 
     @torch.no_grad()
     def load_state_dict(self, state_dict):
@@ -392,6 +484,11 @@ class FlatAdam(Optimizer):
             scale, tracker, skipped = self._ls["init_scale"], 0, 0
         self._write_state(scale=scale, tracker=tracker, step=step,
                           skipped=skipped)
+        if self._clip is not None:
+            # the threshold stays the constructor's; only the counter moves
+            gc = state_dict.get("grad_clip") or {}
+            self._clip.zero_()
+            self._clip[CLIPPED] = float(gc.get("clipped_steps", 0))
 
 
 class FlatAdamW(FlatAdam):
@@ -399,7 +496,9 @@ class FlatAdamW(FlatAdam):
     default ``weight_decay``."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=1e-2, amsgrad=False, loss_scale=None):
+                 weight_decay=1e-2, amsgrad=False, loss_scale=None,
+                 max_grad_norm=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps,
                          weight_decay=weight_decay, amsgrad=amsgrad,
-                         decoupled=True, loss_scale=loss_scale)
+                         decoupled=True, loss_scale=loss_scale,
+                         max_grad_norm=max_grad_norm)

@@ -11,11 +11,16 @@ visible:
                                                        FlatAdam: the baseline)
     flat         FlatAdam, loss scaling off           (2 launches)
     flat_scaled  FlatAdam, loss scaling on            (3 launches)
+    flat_clip         FlatAdam, gradient-norm clipping     (4 launches)
+    flat_scaled_clip  FlatAdam, loss scaling and clipping  (4 launches)
+
+The clipping arms clip on every replay (max_grad_norm 1.0 against a seeded
+gradient of norm 1.3).
 
 Reports microseconds per step per arm and repeat, the bytes the algorithm
 has to move (fp32 streams x 4n, computed from the shapes) over that time
 against the 6.29 TB/s measured copy rate, and - with ``--launch-counts`` -
-the kernel launches per replay, taken from one
+the kernel launches per replay and each kernel's mean time, taken from one
 ``rocprofv3 --kernel-trace --stats`` run per arm of this script itself
 (``--profile-arm``, a fresh child process each; timing is done with the
 profiler off).
@@ -34,11 +39,14 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 
-ARMS = ("adam", "flat", "flat_scaled")
+ARMS = ("adam", "flat", "flat_scaled", "flat_clip", "flat_scaled_clip")
+CLIP_MAX_NORM = 1.0
 COPY_RATE_TBS = 6.29  # measured device copy rate, MI355X
 # fp32 streams of length n one step has to move: read p, g, m, v and write
-# p, m, v; the finite check reads g once more
-STREAMS = {"adam": 7, "flat": 7, "flat_scaled": 8}
+# p, m, v; the finite check, or the stats pass that replaces it with
+# clipping on, reads g once more
+STREAMS = {"adam": 7, "flat": 7, "flat_scaled": 8, "flat_clip": 8,
+           "flat_scaled_clip": 8}
 
 
 def build_arm(name, device):
@@ -62,8 +70,9 @@ def build_arm(name, device):
         for p, g in zip(params, grads):
             p.grad = g
     else:
-        ls = {} if name == "flat_scaled" else None
-        opt = FlatAdam(params, lr=1e-3, loss_scale=ls)
+        ls = {} if "scaled" in name else None
+        clip = CLIP_MAX_NORM if name.endswith("clip") else None
+        opt = FlatAdam(params, lr=1e-3, loss_scale=ls, max_grad_norm=clip)
         scale = opt.loss_scale_value
         with torch.no_grad():
             for p, g in zip(params, grads):
@@ -113,15 +122,17 @@ def launch_counts(replays, out_dir, timeout):
         stats = sorted(prof.rglob(f"{arm}_kernel_stats.csv"))
         if not stats:
             raise RuntimeError(f"no {arm}_kernel_stats.csv under {prof}")
-        per_kernel = {}
+        per_kernel, mean_us = {}, {}
         with open(stats[-1], newline="") as f:
             for row in csv.DictReader(f):
                 k = int(row["Calls"]) // replays
                 if k:  # instantiations sharing the 80-char prefix add up
                     key = row["Name"][:80]
                     per_kernel[key] = per_kernel.get(key, 0) + k
+                    if row.get("AverageNs"):
+                        mean_us[key] = round(float(row["AverageNs"]) / 1e3, 2)
         counts[arm] = {"launches_per_step": sum(per_kernel.values()),
-                       "kernels": per_kernel}
+                       "kernels": per_kernel, "kernel_mean_us": mean_us}
         # the raw trace is large; the aggregated stats are the evidence
         for fn in prof.rglob(f"{arm}_*"):
             if fn.is_file() and not fn.name.endswith("_stats.csv"):
@@ -188,8 +199,15 @@ def main():
         }
         if counts:
             result["arms"][name]["kernels"] = counts[name]["kernels"]
+            result["arms"][name]["kernel_mean_us"] = \
+                counts[name]["kernel_mean_us"]
     opt = arms["flat_scaled"][0]
     result["flat_scaled_skipped_steps"] = opt.skipped_steps
+    for name in ("flat_clip", "flat_scaled_clip"):
+        opt = arms[name][0]
+        result[f"{name}_grad_norm"] = round(opt.grad_norm_value, 6)
+        result[f"{name}_clipped_steps"] = opt.clipped_steps
+        result[f"{name}_skipped_steps"] = opt.skipped_steps
     with open(out_dir / "bench_optim.json", "w") as f:
         json.dump(result, f, indent=2)
 
@@ -203,6 +221,10 @@ def main():
               f" | {r['launches_per_step'] if counts else 'not counted'} | "
               f"{r['bytes_per_step'] / 1e6:.1f} | {r['tb_per_s_at_min']:.2f}"
               f" | {100 * r['share_of_copy_rate']:.0f}% |")
+    if counts:
+        for name in ARMS:
+            print(f"kernel mean us, {name}: "
+                  f"{json.dumps(counts[name]['kernel_mean_us'])}")
     print(json.dumps({k: v for k, v in result.items() if k != "arms"}
                      | {"min_us": {n: r["min_us"]
                                    for n, r in result["arms"].items()}}))
