@@ -19,6 +19,10 @@ work) plus a JSON metadata file:
       images.npy      (uint8)    [M, H, W] frames (optional)
       image_ts.npy    (float64)  [M] frame timestamps (optional)
 
+`EventStoreWriter.add_group` writes a group in one call;
+`EventStoreWriter.open_group` streams one piece by piece (.npy headers written
+last into a reserved region), for outputs that do not fit in host memory.
+
 Groups follow the reference's naming: 'ori', 'down2', 'down4', 'down8',
 'down16' (and 'down8_real' for real-sensor captures).
 """
@@ -57,6 +61,12 @@ class EventStoreWriter:
                     np.asarray(arr).astype(dt, copy=False))
         self.meta["groups"][prefix] = int(n)
 
+    def open_group(self, prefix: str) -> "GroupAppender":
+        """A group written piece by piece (`append`, then `close`), for
+        streams that do not fit in host memory.  The files read back exactly
+        as `add_group`'s."""
+        return GroupAppender(self, prefix)
+
     def add_images(self, images, timestamps):
         images = np.asarray(images, dtype=np.uint8)
         np.save(self.path / "images.npy", images)
@@ -67,6 +77,64 @@ class EventStoreWriter:
     def close(self):
         with open(self.path / "meta.json", "w") as f:
             json.dump(self.meta, f)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+_NPY_HEADER_BYTES = 128      # magic, version, length and a padded dict
+
+
+def _npy_header(dtype, n: int) -> bytes:
+    """A version 1.0 .npy header of exactly _NPY_HEADER_BYTES bytes for a
+    1-D little-endian array of `n` items.  The format lets the dict be
+    padded with spaces before its closing newline, so the size does not
+    depend on `n` and the header can be written after the data."""
+    descr = np.lib.format.dtype_to_descr(np.dtype(dtype))
+    text = (f"{{'descr': {descr!r}, 'fortran_order': False, "
+            f"'shape': ({int(n)},), }}").encode("latin1")
+    room = _NPY_HEADER_BYTES - 10
+    if len(text) + 1 > room:
+        raise ValueError("npy header does not fit its reserved region")
+    text = text + b" " * (room - 1 - len(text)) + b"\n"
+    return b"\x93NUMPY\x01\x00" + len(text).to_bytes(2, "little") + text
+
+
+class GroupAppender:
+    """Streams one event group to its four .npy files.  Each file starts
+    with a reserved header region; `close` writes the headers, now that the
+    length is known, and enters the group into the writer's metadata."""
+
+    def __init__(self, writer: "EventStoreWriter", prefix: str):
+        self.writer = writer
+        self.prefix = prefix
+        self.n = 0
+        self._files = []
+        for name, _ in _FIELDS:
+            f = open(writer.path / f"{prefix}_{name}.npy", "wb")
+            f.write(b"\x00" * _NPY_HEADER_BYTES)
+            self._files.append(f)
+
+    def append(self, xs, ys, ts, ps) -> None:
+        n = len(ts)
+        assert len(xs) == len(ys) == len(ps) == n
+        for f, (_, dt), arr in zip(self._files, _FIELDS, (xs, ys, ts, ps)):
+            a = np.ascontiguousarray(np.asarray(arr).astype(dt, copy=False))
+            f.write(a.astype(a.dtype.newbyteorder("<"), copy=False).tobytes())
+        self.n += n
+
+    def close(self) -> None:
+        if not self._files:
+            return
+        for f, (_, dt) in zip(self._files, _FIELDS):
+            f.seek(0)
+            f.write(_npy_header(np.dtype(dt).newbyteorder("<"), self.n))
+            f.close()
+        self._files = []
+        self.writer.meta["groups"][self.prefix] = int(self.n)
 
     def __enter__(self):
         return self

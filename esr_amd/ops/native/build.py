@@ -21,7 +21,8 @@ SOURCES = [SRC / "bindings.cpp", SRC / "deform_conv.hip",
            SRC / "deform_conv_fused.hip", SRC / "gru_gates.hip",
            SRC / "event_ops.hip", SRC / "conv2d.hip", SRC / "redistribute.hip",
            SRC / "flat_adam.hip", SRC / "stream_ingest.hip",
-           SRC / "batch_splat.hip", SRC / "eval_metrics.hip"]
+           SRC / "batch_splat.hip", SRC / "eval_metrics.hip",
+           SRC / "sr_emit.hip"]
 
 
 def build(verbose: bool = False) -> str:

@@ -93,6 +93,14 @@ int64_t evs_batch_splat_chunk();
 at::Tensor restoration_metrics(const at::Tensor&, const at::Tensor&, double);
 std::vector<int64_t> restoration_metrics_tile();
 
+// sr_emit.hip
+std::vector<at::Tensor> sr_emit_scratch(const at::Tensor&, int64_t, int64_t);
+at::Tensor sr_emit_counts(const at::Tensor&, int64_t);
+void sr_emit_window(const at::Tensor&, const at::Tensor&,
+                    const std::vector<at::Tensor>&, at::Tensor&, int64_t,
+                    int64_t, int64_t, int64_t,
+                    const std::vector<at::Tensor>&);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
         "modulated deformable conv forward (gfx950)");
@@ -159,5 +167,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp32 [P,H,W] maps, fp64 [P,5], deterministic");
   m.def("restoration_metrics_tile", &restoration_metrics_tile,
         "(TH, TW) pixel tile one block of restoration_metrics owns");
+  m.def("sr_emit_scratch", &sr_emit_scratch,
+        "scratch of sr_emit_window for (ncells, capacity), allocated once");
+  m.def("sr_emit_counts", &sr_emit_counts,
+        "the counts stage of sr_emit_window: NaN -> 0, else "
+        "clamp(rint(v), 0, cell_cap), int32 (test hook)");
+  m.def("sr_emit_window", &sr_emit_window,
+        "append one predicted window [2,kH,kW] as sorted event rows to the "
+        "typed chunk columns at a device cursor; int64 offsets, integer "
+        "phases, float64 timestamps, overflow counted; capture-safe");
   m.attr("gfx_arch") = "gfx950";
 }
