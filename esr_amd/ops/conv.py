@@ -32,18 +32,33 @@ ESR_CONV_BWD=native forces all-native, =auto uses native for deep
 stride-1 shapes.  fp32 falls back to torch everywhere (the CPU oracle of
 the parity tests).
 
-fp16 (fp16 autocast, or plain fp16 tensors): the three forward kernels and
-act_grad have an fp16 instantiation (mfma_f32_16x16x32_f16, same tiles and
-LDS layout, fp32 accumulate, one round-to-nearest-even on store; overflow
-saturates to +/-inf like torch's cast).  The native weight-grad and
-input-grad kernels are bf16-only, so the fp16 backward is ALWAYS native
-act_grad + aten.convolution_backward (MIOpen fp16), whatever ESR_CONV_BWD
-says.  Nothing here scales the loss: fp16 gradients below 6e-8 flush to
-zero unless the trainer's opt-in `loss_scale` config key is set (device-side
-in esr_amd/optim FlatAdam, torch.amp.GradScaler otherwise).
+Bias grad: both backward branches take db from the native kernels, not
+from aten.  With an activation, act_grad_bias writes dpre (act_grad's
+arithmetic, bit-equal) and sums the rounded values per channel in the same
+pass; without one, bias_grad is a read-only pass over dy.  Both reduce in
+two stages in a fixed order (no atomics, two runs bit-equal; chain length in
+conv2d.hip; a gradient with B*H*W >= 2^31 - 4096 per channel, or a chain
+above 2^11, is an error there, not a fall-back to torch's sum, and the DCN
+bias shares that), and aten.convolution_backward is called with
+output_mask[2] = False, which drops ATen's strided NCHW sum((0,2,3)) over
+dpre (8.15 ms, 6.3 % of the flagship step's kernel time; the native bias
+grads take 1.23 ms — profiles/README.md, "conv bias gradient").
+
+fp16 (fp16 autocast, or plain fp16 tensors): the three forward kernels,
+act_grad, act_grad_bias and bias_grad have an fp16 instantiation
+(mfma_f32_16x16x32_f16, same tiles and LDS layout, fp32 accumulate, one
+round-to-nearest-even on store; overflow saturates to +/-inf like torch's
+cast).  The native weight-grad and input-grad kernels are bf16-only, so the
+fp16 backward is ALWAYS native act_grad(_bias) + aten.convolution_backward
+(MIOpen fp16), whatever ESR_CONV_BWD says.  Nothing here scales the loss:
+fp16 gradients below 6e-8 flush to zero unless the trainer's opt-in
+`loss_scale` config key is set (device-side in esr_amd/optim FlatAdam,
+torch.amp.GradScaler otherwise).
 
 Env: ESR_NATIVE_CONV=0 disables the native path (A/B benching);
      ESR_CONV_BWD=native routes the bf16 backward to the native kernels;
+     ESR_BIAS_GRAD=aten takes the bias grad from aten.convolution_backward
+     again (A/B; default native, see _BIAS_GRAD_DEFAULT);
      ESR_NATIVE_FP16=0 restores the MIOpen fall-back (and the fp32-island
      deformable conv) for fp16 only; default on (see _FP16_DEFAULT).
 """
@@ -63,7 +78,9 @@ ACT_IDS = {None: 0, "none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 
 # dispatch telemetry: tests / profiling assert the native path really runs
 # ("native_calls_fp16" counts the fp16 subset, in addition to native_calls)
-stats = {"native_calls": 0, "native_calls_fp16": 0}
+# "native_bias_grad" counts backward calls whose bias grad came from
+# act_grad_bias / bias_grad
+stats = {"native_calls": 0, "native_calls_fp16": 0, "native_bias_grad": 0}
 
 _MFMA_MIN_COUT = 32   # below this the MFMA M-tile would idle; use VALU
 _CIK = 32             # K-chunk of the MFMA kernel (pad Cin up to this)
@@ -77,8 +94,21 @@ _CIK = 32             # K-chunk of the MFMA kernel (pad Cin up to this)
 _FP16_DEFAULT = "1"
 
 
+# Default of ESR_BIAS_GRAD: "native" = act_grad_bias / bias_grad, "aten" =
+# the bias output of aten.convolution_backward (a strided NCHW reduce_kernel
+# pass over dpre).  Flagship step end to end, parent and tree alternated
+# three times: 130.82 / 130.86 / 130.71 ms on aten, 124.13 / 124.02 /
+# 123.61 ms native (-6.9 ms, 5.3 %; ranges 0.15 / 0.52 ms, no overlap) —
+# profiles/README.md, "conv bias gradient".
+_BIAS_GRAD_DEFAULT = "native"
+
+
 def _enabled() -> bool:
     return os.environ.get("ESR_NATIVE_CONV", "1") != "0"
+
+
+def _native_bias_grad() -> bool:
+    return os.environ.get("ESR_BIAS_GRAD", _BIAS_GRAD_DEFAULT) != "aten"
 
 
 def native_fp16_enabled() -> bool:
@@ -159,7 +189,20 @@ class _NativeConv2dFn(torch.autograd.Function):
         ks = w.shape[2]
         cout, cin = w.shape[0], w.shape[1]
         dy = dy.contiguous()
-        dpre = ext.act_grad(dy, y, act_id) if act_id else dy
+        # bias grad: per-channel sum of the rounded dpre, produced by the
+        # pass that writes dpre (act_grad_bias), or by a read-only pass over
+        # dy when there is no activation (bias_grad)
+        fused_db = ctx.has_bias and _native_bias_grad()
+        db = None
+        if fused_db:
+            stats["native_bias_grad"] += 1
+            if act_id:
+                dpre, db = ext.act_grad_bias(dy, y, act_id)[:2]
+            else:
+                dpre, db = dy, ext.bias_grad(dy)[0]
+        else:
+            dpre = ext.act_grad(dy, y, act_id) if act_id else dy
+        aten_db = ctx.has_bias and not fused_db
 
         # default aten: the native backward kernels (v2) are oracle-correct
         # but still measured behind MIOpen's wrw/bwd igemm on the deep
@@ -172,11 +215,11 @@ class _NativeConv2dFn(torch.autograd.Function):
             # wgrad/dgrad kernels are bf16-only: fp16 always takes aten
             native_bwd = False
         if not native_bwd:
-            dx, dw, db = torch.ops.aten.convolution_backward(
-                dpre, x, w, [cout] if ctx.has_bias else None,
+            dx, dw, db_aten = torch.ops.aten.convolution_backward(
+                dpre, x, w, [cout] if aten_db else None,
                 [stride, stride], [ks // 2, ks // 2], [1, 1], False, [0, 0],
-                1, [True, True, ctx.has_bias])
-            return dx, dw, db if ctx.has_bias else None, None, None
+                1, [True, True, aten_db])
+            return dx, dw, db_aten if aten_db else db, None, None
 
         # --- native backward path (ESR_CONV_BWD=native) ---
         # input grad: stride-1 is this conv with flipped/transposed weights
@@ -197,8 +240,8 @@ class _NativeConv2dFn(torch.autograd.Function):
         dwp = ext.conv2d_wgrad_mfma(x, dpre, ks, stride,
                                     _ceil(cin, 16), _ceil(cout, 16))
         dw = dwp.permute(1, 0, 2, 3)[:cout, :cin].to(w.dtype)
-        db = dpre.sum(dim=(0, 2, 3), dtype=torch.float32).to(w.dtype) \
-            if ctx.has_bias else None
+        if aten_db:
+            db = dpre.sum(dim=(0, 2, 3), dtype=torch.float32).to(w.dtype)
         return dx, dw, db, None, None
 
 

@@ -59,6 +59,11 @@ at::Tensor conv2d_dgrad_s2(const at::Tensor&, const at::Tensor&,
 at::Tensor conv2d_wgrad_mfma(const at::Tensor&, const at::Tensor&,
                              int64_t, int64_t, int64_t, int64_t);
 at::Tensor act_grad(const at::Tensor&, const at::Tensor&, int64_t);
+std::vector<at::Tensor> act_grad_bias(const at::Tensor&, const at::Tensor&,
+                                      int64_t, bool);
+std::vector<at::Tensor> bias_grad(const at::Tensor&, bool);
+int64_t bias_grad_chain(int64_t, int64_t, int64_t);
+int64_t bias_grad_chunk();
 at::Tensor gemm16_probe(const at::Tensor&, const at::Tensor&);
 
 // redistribute.hip
@@ -134,6 +139,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_wgrad_mfma", &conv2d_wgrad_mfma,
         "bf16 conv weight-grad, MFMA split-K + fp32 atomics (gfx950)");
   m.def("act_grad", &act_grad, "fused activation backward (bf16/fp16)");
+  m.def("act_grad_bias", &act_grad_bias,
+        "activation backward + per-channel bias grad in one pass: "
+        "{dpre, db}, with want_f32 also the fp32 sums; deterministic "
+        "(bf16/fp16)",
+        py::arg("dy"), py::arg("y"), py::arg("act"),
+        py::arg("want_f32") = false);
+  m.def("bias_grad", &bias_grad,
+        "per-channel sum of an NCHW gradient: {db}, with want_f32 also the "
+        "fp32 sums; deterministic (bf16/fp16)",
+        py::arg("dy"), py::arg("want_f32") = false);
+  m.def("bias_grad_chunk", &bias_grad_chunk,
+        "elements of a channel one block of bias_grad sums");
+  m.def("bias_grad_chain", &bias_grad_chain,
+        "longest fp32 addition chain of bias_grad for (B, H, W)");
   m.def("gemm16_probe", &gemm16_probe, "16x16x32 bf16/fp16 MFMA fragment probe");
   m.def("redistribute_stack_hip", &redistribute_stack_hip,
         "count stack -> sorted event cloud, device-only "

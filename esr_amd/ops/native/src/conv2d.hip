@@ -750,18 +750,150 @@ __global__ void conv2d_wgrad_reduce_kernel(
 // Activation backward: dpre = dy * act'(y) elementwise, bf16 or fp16.
 // ---------------------------------------------------------------------------
 
+// dy * act'(y) in fp32, act' written in the activated value y; the one
+// expression both act_grad_kernel and act_grad_bias_kernel evaluate
+template <int ACT> ESR_INLINE float act_grad_value(float g, float v) {
+  if (ACT == 0) return g;
+  if (ACT == 1) return v > 0.f ? g : 0.f;
+  if (ACT == 2) return g * v * (1.f - v);
+  return g * (1.f - v * v);  // tanh
+}
+
+// One dpre element, 16-bit in and out.  The empty asm keeps d an fp32 value
+// of its own: without it hipcc folds the last multiply and the fp16 store
+// conversion into one v_fma_mixlo_f16 in some loops (one rounding of the
+// exact product) and keeps v_mul_f32 + v_cvt_f16_f32 in others (two
+// roundings, the unrolled body of act_grad_kernel), and about one fp16
+// element in 2^14 then differs in its last bit between two kernels, or
+// between the unrolled body and the remainder loop of one kernel.  With it
+// every path rounds the fp32 result once, as the file header says.
+template <typename E, int ACT>
+ESR_INLINE ushort act_grad_elem(ushort dy, ushort y) {
+  float d = act_grad_value<ACT>(E::to_f(dy), E::to_f(y));
+  asm("" : "+v"(d));
+  return E::from_f(d);
+}
+
 template <typename E, int ACT>
 __global__ void act_grad_kernel(long long n, const ushort* __restrict__ dy,
                                 const ushort* __restrict__ y,
                                 ushort* __restrict__ dpre) {
   ESR_KERNEL_LOOP(i, n) {
-    const float g = E::to_f(dy[i]);
-    const float v = E::to_f(y[i]);
-    float d;
-    if (ACT == 1) d = v > 0.f ? g : 0.f;
-    else if (ACT == 2) d = g * v * (1.f - v);
-    else d = g * (1.f - v * v);  // tanh
-    dpre[i] = E::from_f(d);
+    dpre[i] = act_grad_elem<E, ACT>(dy[i], y[i]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Activation backward fused with the conv bias gradient, and the bias
+// gradient alone (ACT == 0, no store): one pass over NCHW [B,C,H,W].
+//
+//   dpre = dy * act'(y)             (act_grad_kernel's arithmetic and rounding)
+//   db[c] = sum_{b,h,w} dpre[b,c,h,w]   over the ROUNDED dpre, i.e. exactly
+//                                       what the dW / dx kernels consume
+//
+// Work item: channel c's B planes laid end to end are a row of L = B*H*W
+// elements, cut into chunks of BG_CHUNK = 256 threads x BG_VPT x 8 elements;
+// item = (c, chunk), P = ceil(L / BG_CHUNK) chunks per channel.  A chunk may
+// cover part of one plane or several planes of its channel.  With H*W % 8 == 0
+// every plane is 16-byte aligned and an 8-element group never straddles two
+// planes: 16-byte loads/stores.  Otherwise (5x33: plane 1 starts 330 B in) a
+// scalar path walks the same chunk element by element.  Items past the grid
+// cap are taken by a grid-stride loop.
+//
+// Deterministic two-stage reduction, no atomics.  Stage 1 writes one fp32
+// partial per item, part[c*P + chunk]; bias_grad_reduce_kernel (one block per
+// channel) adds a channel's P partials in a fixed order and rounds once.
+// Longest chain of dependent fp32 additions behind one db element:
+//   stage 1: 8*BG_VPT per lane + 6 shuffle levels + 3 (4 wave sums in LDS)
+//   stage 2: ceil(P/256) per lane + 6 shuffle levels + 3
+//   n = 8*BG_VPT + 18 + ceil(P/256)
+// (34 + ceil(P/256) at BG_VPT = 2; B768 C64 64x64: P = 768, n = 37).  The host
+// refuses shapes with n > 2^11, the chain cap tests/bound_rules.py assumes.
+// ---------------------------------------------------------------------------
+
+constexpr int BG_VPT = 2;                        // 16-byte groups per thread
+constexpr int BG_CHUNK = ESR_BLOCK * BG_VPT * 8; // elements per work item
+
+// sum over the block's 256 threads in a fixed order; result valid in thread 0
+ESR_INLINE float bg_block_sum(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();  // red may still be read from the previous item
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+template <typename E, int ACT, bool STORE>
+__global__ __launch_bounds__(ESR_BLOCK)
+void act_grad_bias_kernel(int C, unsigned int HW, unsigned int L,
+                          unsigned int P, bool vec,
+                          const ushort* __restrict__ dy,
+                          const ushort* __restrict__ y,
+                          ushort* __restrict__ dpre,
+                          float* __restrict__ part) {
+  __shared__ float red[ESR_BLOCK / 64];
+  const long long nitem = (long long)C * P;
+  for (long long item = blockIdx.x; item < nitem; item += gridDim.x) {
+    const int c = (int)(item / P);
+    const unsigned int e0 = (unsigned int)(item % P) * BG_CHUNK;
+    float acc = 0.f;
+    if (vec) {
+#pragma unroll
+      for (int k = 0; k < BG_VPT; ++k) {
+        const unsigned int e = e0 + (k * ESR_BLOCK + threadIdx.x) * 8;
+        if (e < L) {  // L % 8 == 0: a group is all inside or all outside
+          const unsigned int b = e / HW;
+          const long long a = ((long long)b * C + c) * HW + (e - b * HW);
+          s16x8 g8 = *(const s16x8*)(dy + a);
+          if (ACT != 0) {
+            const s16x8 y8 = *(const s16x8*)(y + a);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              g8[j] = (short)act_grad_elem<E, ACT>((ushort)g8[j],
+                                                   (ushort)y8[j]);
+          }
+          if (STORE) *(s16x8*)(dpre + a) = g8;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc += E::to_f((ushort)g8[j]);
+        }
+      }
+    } else {
+      for (int k = 0; k < BG_VPT * 8; ++k) {
+        const unsigned int e = e0 + k * ESR_BLOCK + threadIdx.x;
+        if (e < L) {
+          const unsigned int b = e / HW;
+          const long long a = ((long long)b * C + c) * HW + (e - b * HW);
+          ushort d = dy[a];
+          if (ACT != 0)
+            d = act_grad_elem<E, ACT>(d, y[a]);
+          if (STORE) dpre[a] = d;
+          acc += E::to_f(d);
+        }
+      }
+    }
+    const float s = bg_block_sum(acc, red);
+    if (threadIdx.x == 0) part[item] = s;
+  }
+}
+
+// stage 2: block c adds part[c*P .. c*P+P) in index order (lane t takes
+// t, t+256, ...; then the same tree as stage 1) and rounds the sum once to
+// the bias dtype; sum32 (may be null) receives the fp32 sum for the tests
+template <typename E>
+__global__ __launch_bounds__(ESR_BLOCK)
+void bias_grad_reduce_kernel(unsigned int P, const float* __restrict__ part,
+                             float* __restrict__ sum32,
+                             ushort* __restrict__ db) {
+  __shared__ float red[ESR_BLOCK / 64];
+  const float* p = part + (long long)blockIdx.x * P;
+  float acc = 0.f;
+  for (unsigned int i = threadIdx.x; i < P; i += ESR_BLOCK) acc += p[i];
+  const float s = bg_block_sum(acc, red);
+  if (threadIdx.x == 0) {
+    if (sum32) sum32[blockIdx.x] = s;
+    db[blockIdx.x] = E::from_f(s);
   }
 }
 
@@ -1093,6 +1225,100 @@ at::Tensor act_grad(const at::Tensor& dy, const at::Tensor& y, int64_t act) {
   });
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return dpre;
+}
+
+int64_t bias_grad_chunk() { return BG_CHUNK; }
+
+// longest chain of dependent fp32 additions behind one db element of
+// act_grad_bias / bias_grad for a [B,C,H,W] gradient (formula: see
+// act_grad_bias_kernel)
+int64_t bias_grad_chain(int64_t B, int64_t H, int64_t W) {
+  const int64_t P = (B * H * W + BG_CHUNK - 1) / BG_CHUNK;
+  return 8 * BG_VPT + 18 + (P + ESR_BLOCK - 1) / ESR_BLOCK;
+}
+
+// shared body: dy [B,C,H,W] bf16|fp16 (y likewise when act != 0).  Returns
+// {dpre (only when store), db [C] in dy's dtype, and with want_f32 the fp32
+// sums [C] before the rounding}.  No host sync; scratch from at::empty
+// (capture-safe).  A shape past the limits below is an error, not a
+// fall-back to torch's sum.
+static std::vector<at::Tensor> bias_grad_impl(const at::Tensor& dy,
+                                              const at::Tensor* y,
+                                              int64_t act, bool store,
+                                              bool want_f32,
+                                              const char* name) {
+  check_16bit(dy, name);
+  TORCH_CHECK(dy.dim() == 4, name, ": [B,C,H,W] tensor required");
+  TORCH_CHECK(act >= 0 && act <= 3, name, ": act id ", act);
+  if (act != 0) {
+    check_16bit(*y, name);
+    check_same_dtype(dy, *y, name);
+    TORCH_CHECK(dy.sizes() == y->sizes(), name, ": dy and y sizes differ");
+  }
+  const int64_t B = dy.size(0), C = dy.size(1), HW = dy.size(2) * dy.size(3);
+  const int64_t L = B * HW;
+  TORCH_CHECK(L > 0 && C > 0, name, ": empty tensor");
+  TORCH_CHECK(L < (1LL << 31) - BG_CHUNK, name,
+              ": B*H*W per channel must stay below 2^31, got ", L);
+  TORCH_CHECK(bias_grad_chain(B, dy.size(2), dy.size(3)) <= 2048, name,
+              ": fp32 summation chain above 2^11");
+  const int64_t P = (L + BG_CHUNK - 1) / BG_CHUNK;
+  at::Tensor dpre;
+  if (store) dpre = at::empty_like(dy);
+  auto f32 = dy.options().dtype(at::kFloat);
+  auto part = at::empty({C * P}, f32);
+  at::Tensor sum32;
+  if (want_f32) sum32 = at::empty({C}, f32);
+  auto db = at::empty({C}, dy.options());
+  const ushort* yp = act != 0 ? (const ushort*)y->data_ptr() : nullptr;
+  ushort* dp = store ? (ushort*)dpre.data_ptr() : nullptr;
+  // 16-byte path: planes 16-byte aligned relative to 16-byte aligned bases
+  const bool vec = HW % 8 == 0 && (uintptr_t)dy.data_ptr() % 16 == 0 &&
+                   (uintptr_t)yp % 16 == 0 && (uintptr_t)dp % 16 == 0;
+  const long long nitem = C * P;
+  const int grid = (int)(nitem < ESR_MAX_BLOCKS ? nitem : ESR_MAX_BLOCKS);
+  auto stream = at::hip::getCurrentHIPStream();
+  DISPATCH_ELEM(dy.scalar_type(), [&] {
+    DISPATCH_ACT((int)act, [&] {
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(ESR_BLOCK), 0, stream,
+                           (int)C, (unsigned int)HW, (unsigned int)L,
+                           (unsigned int)P, vec,
+                           (const ushort*)dy.data_ptr(), yp, dp,
+                           part.data_ptr<float>());
+      };
+      if (store) launch(act_grad_bias_kernel<elem_t, kAct, true>);
+      else launch(act_grad_bias_kernel<elem_t, kAct, false>);
+      return 0;
+    });
+    hipLaunchKernelGGL(bias_grad_reduce_kernel<elem_t>, dim3((int)C),
+                       dim3(ESR_BLOCK), 0, stream, (unsigned int)P,
+                       part.data_ptr<float>(),
+                       want_f32 ? sum32.data_ptr<float>() : nullptr,
+                       (ushort*)db.data_ptr());
+    return 0;
+  });
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  std::vector<at::Tensor> out;
+  if (store) out.push_back(dpre);
+  out.push_back(db);
+  if (want_f32) out.push_back(sum32);
+  return out;
+}
+
+// {dpre, db[, fp32 sums]}: dpre bit-equal to act_grad(dy, y, act), db its
+// per-channel sum
+std::vector<at::Tensor> act_grad_bias(const at::Tensor& dy,
+                                      const at::Tensor& y, int64_t act,
+                                      bool want_f32) {
+  TORCH_CHECK(act != 0, "act_grad_bias: act 0 has no dpre to write, "
+              "use bias_grad");
+  return bias_grad_impl(dy, &y, act, true, want_f32, "act_grad_bias");
+}
+
+// {db[, fp32 sums]} of a conv without activation: read-only pass over dy
+std::vector<at::Tensor> bias_grad(const at::Tensor& dy, bool want_f32) {
+  return bias_grad_impl(dy, nullptr, 0, false, want_f32, "bias_grad");
 }
 
 at::Tensor gemm16_probe(const at::Tensor& A, const at::Tensor& B) {

@@ -597,6 +597,9 @@ at::Tensor deform_conv2d_forward_fused(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const c10::optional<at::Tensor>&, int64_t);
 
+// conv2d.hip
+std::vector<at::Tensor> bias_grad(const at::Tensor&, bool);
+
 namespace {
 
 DcnGeom dcn_forward_geom(
@@ -761,7 +764,12 @@ std::vector<at::Tensor> deform_conv2d_backward_cols(
   }
   auto grad_weight = at::bmm(go2d, cols.transpose(1, 2)).sum(0)
                          .reshape(weight.sizes());
-  auto grad_bias = grad_out.sum(at::IntArrayRef{0, 2, 3});
+  // 16-bit: the conv bias-grad kernels (conv2d.hip, deterministic two-stage
+  // sum); fp32 keeps torch's reduction
+  const bool g16 = grad_out.scalar_type() == at::kBFloat16 ||
+                   grad_out.scalar_type() == at::kHalf;
+  auto grad_bias = g16 ? bias_grad(grad_out.contiguous(), false)[0]
+                       : grad_out.sum(at::IntArrayRef{0, 2, 3});
 
   return {grad_input, grad_offset, grad_mask, grad_weight, grad_bias};
 }

@@ -9,6 +9,10 @@ NCHW) forward and fwd+bwd times.
 kernels vs MIOpen fp16); --wgrad stays bf16 (the native weight-grad kernel
 is bf16-only).
 
+--bias-grad times the conv bias gradient at the same call sites:
+act_grad + dpre.sum((0,2,3)) against act_grad_bias (bias_grad where the conv
+has no activation), with the bytes each must move over the kernel time.
+
 Usage (GPU box): python tools/bench_conv.py [--iters 50] [--dtype fp16]
 """
 
@@ -133,6 +137,58 @@ def wgrad_component(args):
         print(f"{label:34s} {tn:10.3f} {tt:10.3f} {tt / tn:6.2f}")
 
 
+HBM_PEAK_TBS = 8.0   # MI355X HBM3E peak
+
+
+def bias_grad_component(args):
+    """Bias gradient at the flagship call sites: today's two passes
+    (act_grad, then torch's strided sum over dpre) against the fused pass.
+    Bytes that must move: 3*|dpre| fused (read dy and y, write dpre),
+    1*|dpre| for the read-only bias_grad of a conv without activation."""
+    from esr_amd.ops.conv import ACT_IDS
+    from esr_amd.ops.native import require_ext
+    ext = require_ext()
+    dev = "cuda:0"
+    dt = DTYPES[args.dtype]
+    torch.manual_seed(0)
+    print(f"{'shape':34s} {'MB':>7s} {'old ms':>8s} {'new ms':>8s} "
+          f"{'x':>6s} {'TB/s':>6s} {'of peak':>8s}")
+    tot_o = tot_n = 0.0
+    for label, B, cin, cout, h, w, ks, stride, act in SHAPES:
+        ho = (h + 2 * (ks // 2) - ks) // stride + 1
+        wo = (w + 2 * (ks // 2) - ks) // stride + 1
+        dy = torch.randn(B, cout, ho, wo, device=dev).to(dt)
+        y = None
+        if act:
+            act_fn = {"relu": torch.relu, "sigmoid": torch.sigmoid,
+                      "tanh": torch.tanh}[act]
+            y = act_fn(torch.randn_like(dy, dtype=torch.float32)).to(dt)
+        aid = ACT_IDS[act]
+
+        def old():
+            dpre = ext.act_grad(dy, y, aid) if aid else dy
+            return dpre.sum((0, 2, 3))
+
+        def new():
+            if aid:
+                return ext.act_grad_bias(dy, y, aid)[1]
+            return ext.bias_grad(dy)[0]
+
+        ref = old().float()
+        err = (new().float() - ref).abs().max().item()
+        assert err <= 2.0 ** -6 * ref.abs().max().item() + 1e-3, (label, err)
+        nbytes = dy.numel() * 2 * (3 if aid else 1)
+        to = bench(old, args.iters)
+        tn = bench(new, args.iters)
+        tbs = nbytes / (tn * 1e-3) / 1e12
+        tot_o += to
+        tot_n += tn
+        print(f"{label:34s} {nbytes / 1e6:7.1f} {to:8.3f} {tn:8.3f} "
+              f"{to / tn:6.2f} {tbs:6.2f} {tbs / HBM_PEAK_TBS:8.1%}")
+    print(f"{'TOTAL':34s} {'':7s} {tot_o:8.3f} {tot_n:8.3f} "
+          f"{tot_o / tot_n:6.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
@@ -141,6 +197,9 @@ def main():
                     help="time the wgrad kernel alone vs aten wgrad-only")
     ap.add_argument("--valu2", action="store_true",
                     help="A/B the tiny-channel strip kernel vs v1 and torch")
+    ap.add_argument("--bias-grad", action="store_true",
+                    help="time act_grad + sum((0,2,3)) against "
+                         "act_grad_bias / bias_grad, with achieved bytes/s")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="bf16",
                     help="operand dtype of the native kernels and of the "
                          "MIOpen comparison (--wgrad stays bf16)")
@@ -150,6 +209,8 @@ def main():
         return wgrad_component(args)
     if args.valu2:
         return valu2_component(args)
+    if args.bias_grad:
+        return bias_grad_component(args)
 
     from esr_amd.ops.conv import ACT_IDS, _NativeConv2dFn
     dev = "cuda:0"
