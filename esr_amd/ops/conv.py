@@ -7,30 +7,39 @@ ReLU/sigmoid/tanh fused into the conv epilogue.
 
 Dispatch (see conv2d.hip; thresholds from tools/bench_conv.py measured on
 MI355X, profiles/README.md):
-  * MFMA implicit-GEMM kernel for Cout >= 32 — measured 1.0-2.0x MIOpen
-    bf16 on the deep/mid shapes;
+  * stride-1 deep class (3x3 pad 1 / 1x1, Cin >= 32 and Cout >= 32, bf16):
+    the 8x32-tile MFMA core conv2d_s1 (16-byte staging loads transposed in
+    registers, patch staged once for all Cout, double-buffered, 16-byte
+    stores) — 1.3-3.3x the older MFMA kernel on every shape, same bits
+    (ESR_CONV_FWD=mfma keeps the older kernel);
+  * MFMA implicit-GEMM kernel conv2d_fwd_mfma for the rest of Cout >= 32
+    (stride 2, Cin < 32, fp16) — measured 1.0-2.0x MIOpen bf16;
   * direct VALU kernel for Cin >= 32 with tiny Cout (attention/kernel
     convs, 1.2-1.3x);
   * register-strip VALU v2 for the tiny-channel class (Cin and Cout both
     < 32): 8-wide output strips x all cout per thread, weights broadcast
     from LDS — head 2.7x, tail 1.3x vs MIOpen; the stride-2 enc1 shape
     (0.67x) stays on MIOpen.
-Backward defaults to torch's aten.convolution_backward (MIOpen bf16).
-The native backward kernels are implemented, oracle-tested and measured
-(tools/bench_conv.py --wgrad / --bwd, MI355X):
-  * weight-grad (conv2d_wgrad_s1: 4-row MFMA chunks, rolling X window,
-    DETERMINISTIC two-stage reduction — no fp32 atomics) reaches
-    0.9-1.1x MIOpen wrw on the wide 32x32 shapes (resblock 1.07x,
-    192->64 1.05x, dense 1.03x) after a 7x optimization ladder driven by
-    ablation (the original per-address atomic flush was 70-87% of the
-    kernel; ESR_WGRAD_ABL still exposes the ablation arms);
-  * stride-1 input-grad reuses the forward kernels with packed
-    flipped/transposed weights; stride-2 dgrad is a VALU gather kernel.
-End-to-end the native backward composition still measures 0.8x of
-MIOpen's fused bwd on the whole shape set, so aten stays the default;
-ESR_CONV_BWD=native forces all-native, =auto uses native for deep
-stride-1 shapes.  fp32 falls back to torch everywhere (the CPU oracle of
-the parity tests).
+Backward (bf16): ESR_CONV_BWD defaults to "auto", which routes per gradient
+by measurement (tools/bench_conv.py --bwd-parts, table at _CONV_BWD_DEFAULT)
+inside the stride-1 deep class and leaves every other class on
+aten.convolution_backward (MIOpen bf16):
+  * input grad, 3x3: conv2d_s1 with dgrad=True — the same core, its pack
+    launch reading the weights flipped and transposed in place (no
+    transpose/flip/permute/pad copies on the host side); 1.4-3.5x aten,
+    whose time includes its NCHW<->NHWC transposes.  The 1x1 stays on aten;
+  * weight grad: conv2d_wgrad_s1 (4-row MFMA chunks, rolling X window,
+    DETERMINISTIC two-stage reduction — no fp32 atomics; the second stage
+    writes [Cout, Cin, k, k] bf16, so no zero fill, permute, slice or cast
+    follows) at Cin >= 192, where it wins by 3-7 %; elsewhere it is
+    0.57-0.95x of MIOpen's wrw and aten is called with
+    output_mask = [False, True, False].  ESR_WGRAD_ABL still exposes the
+    ablation arms of its first stage;
+  * stride-2 input grad is a VALU gather kernel, stride-2 weight grad the
+    older atomic kernel: both only under ESR_CONV_BWD=native.
+ESR_CONV_BWD=native forces every gradient native, =aten every gradient to
+aten.  fp32 falls back to torch everywhere (the CPU oracle of the parity
+tests).
 
 Bias grad: both backward branches take db from the native kernels, not
 from aten.  With an activation, act_grad_bias writes dpre (act_grad's
@@ -56,7 +65,10 @@ fp16 gradients below 6e-8 flush to zero unless the trainer's opt-in
 torch.amp.GradScaler otherwise).
 
 Env: ESR_NATIVE_CONV=0 disables the native path (A/B benching);
-     ESR_CONV_BWD=native routes the bf16 backward to the native kernels;
+     ESR_CONV_BWD=auto (default) | native | aten | dgrad (A/B: input grad
+     native, weight grad aten): bf16 backward routing;
+     ESR_CONV_FWD=auto (default) | core | mfma: forward kernel of the
+     stride-1 deep class;
      ESR_BIAS_GRAD=aten takes the bias grad from aten.convolution_backward
      again (A/B; default native, see _BIAS_GRAD_DEFAULT);
      ESR_NATIVE_FP16=0 restores the MIOpen fall-back (and the fp32-island
@@ -101,6 +113,29 @@ _FP16_DEFAULT = "1"
 # 123.61 ms native (-6.9 ms, 5.3 %; ranges 0.15 / 0.52 ms, no overlap) —
 # profiles/README.md, "conv bias gradient".
 _BIAS_GRAD_DEFAULT = "native"
+
+
+# Default of ESR_CONV_BWD, and what "auto" routes native inside the deep
+# stride-1 class (bf16, 3x3 pad 1 / 1x1, Cin >= 32 and Cout >= 32); every
+# other class stays on aten.  From tools/bench_conv.py --bwd-parts on MI355X
+# at the flagship's per-call batches (profiles/README.md, "conv backward:
+# native default"; ms, whole class summed unless a shape is named):
+#   input grad, 3x3: conv2d_s1 1.4-3.5x aten on every shape (2.05 against
+#     4.03 ms; the older native kernel 4.67) -> native;
+#   input grad, 1x1 128->64: 0.061 against aten's 0.038 -> aten;
+#   weight grad: conv2d_wgrad_s1 wins at Cin 192 only (resblock 0.950
+#     against 1.017, 192->64 0.381 / 0.382 against 0.403 / 0.392) and is
+#     0.57-0.95x elsewhere (gru 128->128 0.831 against 0.626) -> native at
+#     Cin >= 192, 3x3;
+#   whole backward of one conv, act and bias grad included: all aten 9.41,
+#     all native 8.30, this routing 7.62 (put together from those columns).
+_CONV_BWD_DEFAULT = "auto"
+_AUTO_WGRAD_MIN_CIN = 192
+
+# Default of ESR_CONV_FWD: the forward of the same class takes conv2d_s1,
+# 2.03 against 4.91 ms for conv2d_fwd_mfma over the class (1.3-3.3x on every
+# shape, the 1x1 0.039 against 0.061), same bits (same table).
+_CONV_FWD_DEFAULT = "auto"
 
 
 def _enabled() -> bool:
@@ -160,7 +195,10 @@ class _NativeConv2dFn(torch.autograd.Function):
         ks = w.shape[2]
         cout, cin = w.shape[0], w.shape[1]
         bias_f = bias.float() if bias is not None else None
-        if cout >= _MFMA_MIN_COUT:
+        if fwd_core_route(os.environ.get("ESR_CONV_FWD", _CONV_FWD_DEFAULT),
+                          x.dtype == torch.bfloat16, ks, stride, cin, cout):
+            y = ext.conv2d_s1(x, w.contiguous(), bias_f, act_id, False)
+        elif cout >= _MFMA_MIN_COUT:
             y = ext.conv2d_fwd_mfma(x, _pack(w), bias_f, cout, ks, stride,
                                     act_id)
         elif cin < _MFMA_MIN_COUT and x.shape[-1] % 8 == 0:
@@ -204,45 +242,86 @@ class _NativeConv2dFn(torch.autograd.Function):
             dpre = ext.act_grad(dy, y, act_id) if act_id else dy
         aten_db = ctx.has_bias and not fused_db
 
-        # default aten: the native backward kernels (v2) are oracle-correct
-        # but still measured behind MIOpen's wrw/bwd igemm on the deep
-        # shapes (tools/bench_conv.py --bwd); "auto" switches stride-1
-        # deep shapes native once they win
-        mode = os.environ.get("ESR_CONV_BWD", "aten")
-        native_bwd = mode == "native" or (
-            mode == "auto" and stride == 1 and cin >= _MFMA_MIN_COUT)
-        if x.dtype != torch.bfloat16:
-            # wgrad/dgrad kernels are bf16-only: fp16 always takes aten
-            native_bwd = False
-        if not native_bwd:
+        dgrad_native, wgrad_native = bwd_route(
+            os.environ.get("ESR_CONV_BWD", _CONV_BWD_DEFAULT),
+            x.dtype == torch.bfloat16, ks, stride, cin, cout)
+        pad = [ks // 2, ks // 2]
+        if not (dgrad_native and wgrad_native):
+            # aten computes whatever is not routed native; its bias output
+            # only with ESR_BIAS_GRAD=aten
             dx, dw, db_aten = torch.ops.aten.convolution_backward(
                 dpre, x, w, [cout] if aten_db else None,
-                [stride, stride], [ks // 2, ks // 2], [1, 1], False, [0, 0],
-                1, [True, True, aten_db])
-            return dx, dw, db_aten if aten_db else db, None, None
-
-        # --- native backward path (ESR_CONV_BWD=native) ---
-        # input grad: stride-1 is this conv with flipped/transposed weights
-        if stride == 1:
-            wt = w.transpose(0, 1)
-            if ks == 3:
-                wt = wt.flip((2, 3))
-            if cin >= _MFMA_MIN_COUT:
-                dx = ext.conv2d_fwd_mfma(dpre, _pack(wt), None, cin, ks, 1, 0)
-            else:
-                dx = ext.conv2d_fwd_valu(dpre, wt.contiguous(), None, 1, 0)
-        else:
-            dx = ext.conv2d_dgrad_s2(dpre, w.contiguous(),
-                                     x.shape[2], x.shape[3])
-
-        # weight grad: MFMA split-K into padded fp32 (transposed
-        # [Cin_p, Cout_p] scratch for line-parallel atomics), then slice
-        dwp = ext.conv2d_wgrad_mfma(x, dpre, ks, stride,
-                                    _ceil(cin, 16), _ceil(cout, 16))
-        dw = dwp.permute(1, 0, 2, 3)[:cout, :cin].to(w.dtype)
-        if aten_db:
+                [stride, stride], pad, [1, 1], False, [0, 0], 1,
+                [not dgrad_native, not wgrad_native, aten_db])
+            if aten_db:
+                db = db_aten
+        elif aten_db:
             db = dpre.sum(dim=(0, 2, 3), dtype=torch.float32).to(w.dtype)
+
+        if dgrad_native:
+            if stride == 1 and cin >= _MFMA_MIN_COUT:
+                # the 8x32-tile core with the weights indexed flipped and
+                # transposed by its pack launch
+                dx = ext.conv2d_s1(dpre, w.contiguous(), None, 0, True)
+            elif stride == 1:
+                wt = w.transpose(0, 1)
+                if ks == 3:
+                    wt = wt.flip((2, 3))
+                dx = ext.conv2d_fwd_valu(dpre, wt.contiguous(), None, 1, 0)
+            else:
+                dx = ext.conv2d_dgrad_s2(dpre, w.contiguous(),
+                                         x.shape[2], x.shape[3])
+        if wgrad_native:
+            if stride == 1:
+                # two-stage deterministic reduction; the second stage writes
+                # [Cout, Cin, k, k] bf16, rounded once from the fp32 sum
+                dw = ext.conv2d_wgrad_s1(x, dpre, ks)
+            else:
+                # stride 2: split-K into padded transposed fp32, then slice
+                dwp = ext.conv2d_wgrad_mfma(x, dpre, ks, stride,
+                                            _ceil(cin, 16), _ceil(cout, 16))
+                dw = dwp.permute(1, 0, 2, 3)[:cout, :cin].to(w.dtype)
         return dx, dw, db, None, None
+
+
+def bwd_route(mode: str, is_bf16: bool, ks: int, stride: int, cin: int,
+              cout: int) -> tuple[bool, bool]:
+    """Backward half of the dispatch (pure, CPU-testable): (input grad
+    native, weight grad native) for ESR_CONV_BWD = `mode`.
+
+    "aten" and "native" route everything one way, "dgrad" sends only the
+    input grad native (an A/B arm); anything else ("auto", the default)
+    follows the measured table at _CONV_BWD_DEFAULT.  The
+    native wgrad/dgrad kernels are bf16-only: fp16 always takes aten.
+    """
+    if not is_bf16 or mode == "aten":
+        return False, False
+    if mode == "native":
+        return True, True
+    if mode == "dgrad":
+        # A/B arm of tools/bench_conv.py --bwd-parts: input grad native,
+        # weight grad on aten, wherever "native" would apply
+        return True, False
+    deep_s1 = stride == 1 and ks in (1, 3) and \
+        cin >= _MFMA_MIN_COUT and cout >= _MFMA_MIN_COUT
+    if not deep_s1 or ks != 3:
+        return False, False
+    return True, cin >= _AUTO_WGRAD_MIN_CIN
+
+
+def fwd_core_route(mode: str, is_bf16: bool, ks: int, stride: int, cin: int,
+                   cout: int) -> bool:
+    """Forward of the deep stride-1 class on the 8x32-tile core
+    (conv2d_s1) instead of conv2d_fwd_mfma (pure, CPU-testable).
+    ESR_CONV_FWD = "mfma" keeps every shape on the older kernel, "core"
+    and "auto" take the core on the whole class, where it was measured
+    faster on every shape (see _CONV_FWD_DEFAULT).  fp16 stays on the older kernel: the
+    core's fp16 instantiation is built but was not measured."""
+    if mode == "mfma" or not is_bf16:
+        return False
+    deep_s1 = stride == 1 and ks in (1, 3) and \
+        cin >= _MFMA_MIN_COUT and cout >= _MFMA_MIN_COUT
+    return deep_s1
 
 
 def shape_supported(conv: torch.nn.Conv2d, dtype=None) -> bool:

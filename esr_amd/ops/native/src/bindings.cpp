@@ -58,6 +58,9 @@ at::Tensor conv2d_dgrad_s2(const at::Tensor&, const at::Tensor&,
                            int64_t, int64_t);
 at::Tensor conv2d_wgrad_mfma(const at::Tensor&, const at::Tensor&,
                              int64_t, int64_t, int64_t, int64_t);
+at::Tensor conv2d_s1(const at::Tensor&, const at::Tensor&,
+                     const c10::optional<at::Tensor>&, int64_t, bool);
+at::Tensor conv2d_wgrad_s1(const at::Tensor&, const at::Tensor&, int64_t);
 at::Tensor act_grad(const at::Tensor&, const at::Tensor&, int64_t);
 std::vector<at::Tensor> act_grad_bias(const at::Tensor&, const at::Tensor&,
                                       int64_t, bool);
@@ -138,6 +141,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 stride-2 conv input-grad (gfx950)");
   m.def("conv2d_wgrad_mfma", &conv2d_wgrad_mfma,
         "bf16 conv weight-grad, MFMA split-K + fp32 atomics (gfx950)");
+  m.def("conv2d_s1", &conv2d_s1,
+        "bf16/fp16 stride-1 3x3/1x1 conv, 8x32-tile MFMA core: forward with "
+        "fused bias+act, or the input grad (dgrad=True) (gfx950)");
+  m.def("conv2d_wgrad_s1", &conv2d_wgrad_s1,
+        "bf16 stride-1 conv weight grad, deterministic two-stage reduction, "
+        "dW [Cout,Cin,k,k] bf16 (gfx950)");
   m.def("act_grad", &act_grad, "fused activation backward (bf16/fp16)");
   m.def("act_grad_bias", &act_grad_bias,
         "activation backward + per-channel bias grad in one pass: "

@@ -13,7 +13,7 @@
 // dispatch on x.scalar_type() and reject mixed bf16/fp16 operands.  The
 // backward-only kernels (dgrad_s2, wgrad) are bf16-only and say so.
 //
-// Two forward paths, picked by the host by shape:
+// Forward paths, picked by the host by shape:
 //   * MFMA implicit GEMM (mfma_f32_16x16x32_bf16 / _f16): M = Cout tile (32/64),
 //     N = 64 output pixels (2 rows x 32 cols), K = Cin in chunks of 32,
 //     3x3 taps looped outside K.  The input patch is staged in LDS in a
@@ -23,12 +23,16 @@
 //   * VALU direct kernel for bandwidth-bound small-channel shapes
 //     (Cin small or Cout < 16 where MFMA tiles would idle).
 //
-// Backward: stride-1 input-grad IS this forward with flipped/transposed
-// packed weights (host side); stride-2 input-grad has a dedicated
+//   * stride-1 deep class (3x3 / 1x1, >= 32 channels in and out): the
+//     8x32-tile core conv2d_s1_core_kernel, forward and input grad.
+//
+// Backward: the stride-1 input-grad IS the forward with the weights read
+// flipped and transposed (by the core's pack kernel; for Cin < 32 by the
+// VALU kernel on a host-side copy); stride-2 input-grad has a dedicated
 // scatter-form VALU kernel; stride-1 weight-grad is the MFMA kernel with
-// a DETERMINISTIC two-stage reduction (conv2d_wgrad_s1_kernel below),
-// stride-2 weight-grad the older per-row-tile variant with transposed
-// line-parallel atomics.
+// a DETERMINISTIC two-stage reduction (conv2d_wgrad_s1_kernel below) whose
+// second stage writes dW [Cout, Cin, k, k] bf16, stride-2 weight-grad the
+// older per-row-tile variant with transposed line-parallel atomics.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -205,6 +209,265 @@ void conv2d_fwd_mfma_kernel(
         if (bias) v += bias[co];
         v = apply_act<ACT>(v);
         y[(((long long)b * Cout + co) * Ho + oy) * Wo + ox] = E::from_f(v);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Stride-1 MFMA core for the deep class (3x3 pad 1 and 1x1, K >= 32 input
+// and M >= 32 output channels): the stride-1 input grad, and offered to the
+// forward (conv2d_s1 below).
+//
+//   block tile: 8 rows x 32 cols of output pixels x up to 16*MC channels,
+//   wave grid 2 (channel halves) x 2 (rows 0-3 / 4-7); the MFMA's M rows are
+//   PIXELS and its N columns output channels, so one lane ends up with four
+//   neighbouring pixels of one channel.
+//
+// Against conv2d_fwd_mfma_kernel:
+//   * staging reads 16 bytes along W (8 pixels) per load, 8 channels per
+//     thread, and transposes the 8x8 block in registers into the same
+//     pixel-major 80-byte slots; rows that are not 16-byte aligned
+//     (W % 8 != 0) and partial groups take element loads.  The two halo
+//     columns are staged by otherwise idle threads (160 + 80 of 256 busy at
+//     3x3), and the 10-row patch is read once for ALL output channels of the
+//     block (halo amplification 1.25x, no re-staging per 64-channel block;
+//     M is split over blockIdx.z only above 128 channels, where the
+//     accumulators no longer fit);
+//   * two patch buffers: the global loads of chunk k+1 are issued before the
+//     MFMAs of chunk k and written to the other buffer after them, one
+//     barrier per chunk, 72*MC MFMAs per wave between barriers (36 before);
+//   * the epilogue swaps 8 bytes between lane pairs 16 apart and stores 16
+//     bytes (8 pixels) per lane, 64-byte runs per channel row.
+// Accumulation order per output element (chunk-major, then tap, then the
+// MFMA's own 32 channels) is that of conv2d_fwd_mfma_kernel.
+// Weights: conv2d_pack_w_kernel writes [tap][Mp][Kp] once per call, zero
+// padded to the block grid (no row clamp here); for the input grad it reads
+// w[co][ci][KS-1-ky][KS-1-kx] in place, so no flipped or transposed copy is
+// made on the host side.
+// ---------------------------------------------------------------------------
+
+constexpr int C_TH = 8;   // output rows per block tile
+
+ESR_INLINE float apply_act_rt(float v, int act) {
+  switch (act) {   // uniform across the grid
+    case 1: return apply_act<1>(v);
+    case 2: return apply_act<2>(v);
+    case 3: return apply_act<3>(v);
+    default: return v;
+  }
+}
+
+__global__ void conv2d_pack_w_kernel(
+    long long n, const ushort* __restrict__ w,   // [O, I, KS, KS]
+    ushort* __restrict__ wp,                     // [KS*KS, Mp, Kp]
+    int O, int I, int KS, int Mp, int Kp, int dgrad) {
+  ESR_KERNEL_LOOP(i, n) {
+    const int k = (int)(i % Kp);
+    const int m = (int)((i / Kp) % Mp);
+    const int tap = (int)(i / ((long long)Kp * Mp));
+    const int ky = tap / KS, kx = tap % KS;
+    const int o = dgrad ? k : m, ci = dgrad ? m : k;
+    const int sy = dgrad ? KS - 1 - ky : ky, sx = dgrad ? KS - 1 - kx : kx;
+    wp[i] = (o < O && ci < I)
+        ? w[(((long long)o * I + ci) * KS + sy) * KS + sx] : (ushort)0;
+  }
+}
+
+template <typename E, int KS, int MC>
+__global__ __launch_bounds__(256, 2)   // 2 waves/SIMD: two blocks per CU
+void conv2d_s1_core_kernel(
+    const ushort* __restrict__ x,      // [B, Cin, H, W]
+    const ushort* __restrict__ wp,     // [KS*KS, Mp, Kp] from conv2d_pack_w
+    const float* __restrict__ bias,    // [Cout] fp32 or nullptr
+    ushort* __restrict__ y,            // [B, Cout, H, W]
+    int Cin, int H, int W, int Cout, int Kp, int Mp, int ntx, int act,
+    int valign) {   // valign: W % 8 == 0 and both bases 16-byte aligned
+  constexpr int PAD = KS / 2;
+  constexpr int PH = C_TH + 2 * PAD;       // patch rows
+  constexpr int PWC = TW + 2 * PAD;        // patch cols
+  constexpr int MCW = MC / 2;              // channel fragments per wave
+  constexpr int BUF = PH * PWC * SLOT;     // shorts per patch buffer
+  constexpr int NV = PH * 4 * 4;           // 8ch x 8px vector staging units
+  constexpr int NHALO = PAD ? PH * 4 * 2 : 0;  // 8ch x 1px halo units
+  static_assert(NV + NHALO <= 256, "one staging unit per thread");
+  __shared__ __attribute__((aligned(16))) ushort patch[2 * BUF];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int l15 = lane & 15, lg = lane >> 4;
+
+  const int ty0 = (blockIdx.x / ntx) * C_TH;
+  const int tx0 = (blockIdx.x % ntx) * TW;
+  const int b = blockIdx.y;
+  const int co0 = blockIdx.z * (16 * MC);
+
+  const long long plane = (long long)H * W;
+  const ushort* xb = x + (long long)b * Cin * plane;
+
+  // this thread's staging unit (fixed over the chunks)
+  const bool is_vec = tid < NV;
+  const bool is_halo = !is_vec && tid < NV + NHALO;
+  int u_row, u_cg, u_px;   // patch row, 8-channel group, first pixel (global)
+  int u_col;               // patch column of the unit's first pixel
+  if (is_vec) {
+    const int g = tid & 3;
+    u_row = (tid >> 2) % PH;
+    u_cg = tid / (4 * PH);
+    u_px = tx0 + g * 8;
+    u_col = PAD + g * 8;
+  } else {
+    const int h = tid - NV;
+    const int side = h & 1;
+    u_row = (h >> 1) % PH;
+    u_cg = (h >> 1) / PH;
+    u_px = side ? tx0 + TW : tx0 - 1;
+    u_col = side ? PWC - 1 : 0;
+  }
+  const int u_iy = ty0 - PAD + u_row;
+  const bool u_row_ok = u_iy >= 0 && u_iy < H;
+  const bool u_vec_ok = valign && u_px + 8 <= W;
+  const ushort* u_src = xb + (long long)u_iy * W + u_px;
+
+  s16x8 pre[8];   // vector unit: pre[channel][pixel]; halo unit: pre[0][ch]
+
+  auto load_chunk = [&](int ci0) {
+    if (is_vec) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = ci0 + u_cg * 8 + j;
+        s16x8 v = {};
+        if (c < Cin && u_row_ok) {
+          const ushort* src = u_src + c * plane;
+          if (u_vec_ok) {
+            v = *reinterpret_cast<const s16x8*>(src);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              v[e] = (u_px + e < W) ? (short)src[e] : (short)0;
+          }
+        }
+        pre[j] = v;
+      }
+    } else if (is_halo) {
+      s16x8 v = {};
+      if (u_row_ok && u_px >= 0 && u_px < W) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = ci0 + u_cg * 8 + j;
+          v[j] = (c < Cin) ? (short)u_src[c * plane] : (short)0;
+        }
+      }
+      pre[0] = v;
+    }
+  };
+
+  auto store_chunk = [&](ushort* buf) {
+    ushort* dst = buf + (u_row * PWC + u_col) * SLOT + u_cg * 8;
+    if (is_vec) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = pre[j][e];
+        *reinterpret_cast<s16x8*>(dst + e * SLOT) = v;
+      }
+    } else if (is_halo) {
+      *reinterpret_cast<s16x8*>(dst) = pre[0];
+    }
+  };
+
+  f32x4 acc[8][MCW] = {};
+  const int kgrp = lg * 8;
+  const int nchunks = Kp / CIK;
+
+  load_chunk(0);
+  store_chunk(patch);
+  for (int ck = 0; ck < nchunks; ++ck) {
+    // one barrier per chunk: buffer ck&1 is complete, and every wave is done
+    // reading the other one (its MFMAs of chunk ck-1 precede this barrier)
+    __syncthreads();
+    const ushort* cur = patch + (ck & 1) * BUF;
+    const bool more = ck + 1 < nchunks;
+    if (more) load_chunk((ck + 1) * CIK);   // in flight under the MFMAs
+
+    const int ci0 = ck * CIK;
+    // ky stays a loop: fully unrolled, the compiler hoists the fragment
+    // reads of all nine taps and the kernel drops to one wave per SIMD
+#pragma unroll 1
+    for (int ky = 0; ky < KS; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < KS; ++kx) {
+      const int tap = ky * KS + kx;
+      s16x8 wf[MCW];
+#pragma unroll
+      for (int m = 0; m < MCW; ++m) {
+        const int row = co0 + (wm * MCW + m) * 16 + l15;   // < Mp (padded)
+        wf[m] = *reinterpret_cast<const s16x8*>(
+            &wp[((long long)tap * Mp + row) * Kp + ci0 + kgrp]);
+      }
+#pragma unroll
+      for (int nf = 0; nf < 8; ++nf) {
+        const int r = wn * 4 + (nf >> 1);
+        const int col = (nf & 1) * 16 + l15;
+        const s16x8 pf = *reinterpret_cast<const s16x8*>(
+            &cur[((r + ky) * PWC + col + kx) * SLOT + kgrp]);
+#pragma unroll
+        for (int m = 0; m < MCW; ++m)
+          acc[nf][m] = E::mfma(pf, wf[m], acc[nf][m]);
+      }
+    }
+    if (more) store_chunk(patch + ((ck + 1) & 1) * BUF);
+  }
+
+  // ---- epilogue.  D (guide §3): row = pixel (lane>>4)*4 + j of the
+  // fragment's 16, col = channel lane&15.  Fragments 2r and 2r+1 are the two
+  // halves of tile row r: a lane with lg even keeps its four pixels of the
+  // left half and takes the next four from lane+16; a lane with lg odd does
+  // the same on the right half with lane-16.  Every lane then holds 8
+  // neighbouring pixels: lg 0 -> cols 0-7, 2 -> 8-15, 1 -> 16-23, 3 -> 24-31.
+  const bool odd = lg & 1;
+  const int ox0 = tx0 + (odd ? 16 : 0) + (lg >> 1) * 8;
+#pragma unroll
+  for (int m = 0; m < MCW; ++m) {
+    const int co = co0 + (wm * MCW + m) * 16 + l15;
+    const float bv = (bias && co < Cout) ? bias[co] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      unsigned int p[2][2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const ushort lo =
+              E::from_f(apply_act_rt(acc[2 * r + h][m][2 * q] + bv, act));
+          const ushort hi =
+              E::from_f(apply_act_rt(acc[2 * r + h][m][2 * q + 1] + bv, act));
+          p[h][q] = (unsigned int)lo | ((unsigned int)hi << 16);
+        }
+      // all 64 lanes take part in the exchange: no branch above this point
+      const unsigned int s0 = odd ? p[0][0] : p[1][0];
+      const unsigned int s1 = odd ? p[0][1] : p[1][1];
+      const unsigned int r0 = (unsigned int)__shfl_xor((int)s0, 16, 64);
+      const unsigned int r1 = (unsigned int)__shfl_xor((int)s1, 16, 64);
+      unsigned int o[4];
+      o[0] = odd ? r0 : p[0][0];
+      o[1] = odd ? r1 : p[0][1];
+      o[2] = odd ? p[1][0] : r0;
+      o[3] = odd ? p[1][1] : r1;
+      const int oy = ty0 + wn * 4 + r;
+      if (co < Cout && oy < H && ox0 < W) {
+        ushort* dst = y + (((long long)b * Cout + co) * H + oy) * W + ox0;
+        if (valign && ox0 + 8 <= W) {
+          *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (ox0 + e < W)
+              dst[e] = (ushort)(o[e >> 1] >> ((e & 1) * 16));
+        }
       }
     }
   }
@@ -746,6 +1009,34 @@ __global__ void conv2d_wgrad_reduce_kernel(
   }
 }
 
+// The same stage 2, writing the weight's own layout and dtype: i runs over
+// dW [Cout, Cin, k, k] bf16, each element the fp32 sum over g (same order as
+// above) rounded once.  Longest chain of dependent fp32 additions behind one
+// dW element, unchanged by this kernel:
+//   n = 32 (one MFMA product) + fpb*H (MFMAs per block) + ng (partials),
+//   ng = ceil(B/fpb) * ceil(W/32), fpb from the host's grid rule
+// (B768 128->64 32x32: fpb 2, ng 384, n = 480; B384 32->64 64x64: fpb 1,
+// ng 768, n = 864; both under the 2^11 of tests/bound_rules.py).
+template <int NTAP>
+__global__ void conv2d_wgrad_reduce_out_kernel(
+    long long n, const float* __restrict__ part, int ng, int coblks,
+    int Cin, int Cout, ushort* __restrict__ dw) {
+  // i runs over one partial tile set [cib][cob][32ci][64co][tap], so the
+  // reads of every g are contiguous; the (small) dW is written scattered
+  ESR_KERNEL_LOOP(i, n) {
+    const int tap = (int)(i % NTAP);
+    const int co64 = (int)((i / NTAP) % 64);
+    const int ci32 = (int)((i / (NTAP * 64)) % 32);
+    const int blk = (int)(i / (NTAP * 64 * 32));
+    const int ci = (blk / coblks) * 32 + ci32;
+    const int co = (blk % coblks) * 64 + co64;
+    if (ci >= Cin || co >= Cout) continue;
+    float v = 0.f;
+    for (int g = 0; g < ng; ++g) v += part[g * n + i];
+    dw[((long long)co * Cin + ci) * NTAP + tap] = f_to_bf16u(v);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Activation backward: dpre = dy * act'(y) elementwise, bf16 or fp16.
 // ---------------------------------------------------------------------------
@@ -1034,6 +1325,77 @@ at::Tensor conv2d_fwd_mfma(const at::Tensor& x, const at::Tensor& wp,
   return y;
 }
 
+// Stride-1 core (conv2d_s1_core_kernel): 3x3 pad 1 or 1x1.
+//   dgrad == false: y = act(conv(x, w) + bias), x [B,I,H,W], w [O,I,ks,ks]
+//   dgrad == true:  dx = conv_transpose(x = dpre [B,O,H,W], w [O,I,ks,ks]),
+//                   bias none, act 0
+// Two launches: the weight pack and the core.  No host sync, scratch from
+// at::empty (capture-safe).
+at::Tensor conv2d_s1(const at::Tensor& x, const at::Tensor& w,
+                     const c10::optional<at::Tensor>& bias, int64_t act,
+                     bool dgrad) {
+  check_16bit(x, "conv2d_s1: x");
+  check_16bit(w, "conv2d_s1: w");
+  check_same_dtype(x, w, "conv2d_s1: x / w");
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && w.size(2) == w.size(3),
+              "conv2d_s1: x [B,C,H,W], w [O,I,k,k]");
+  const int ks = w.size(2);
+  TORCH_CHECK(ks == 1 || ks == 3, "conv2d_s1: 3x3 or 1x1 only, got ", ks);
+  TORCH_CHECK(act >= 0 && act <= 3, "conv2d_s1: act id ", act);
+  TORCH_CHECK(!dgrad || (!bias.has_value() && act == 0),
+              "conv2d_s1: the input grad takes no bias or activation");
+  const int O = w.size(0), I = w.size(1);
+  const int B = x.size(0), K = x.size(1), H = x.size(2), W = x.size(3);
+  const int M = dgrad ? I : O;
+  TORCH_CHECK(K == (dgrad ? O : I), "conv2d_s1: x has ", K,
+              " channels, w wants ", dgrad ? O : I);
+  TORCH_CHECK(B <= 65535, "conv2d_s1: batch above the grid's y limit");
+  // channel fragments of 16 per block: at most 8 (128 accumulator VGPRs),
+  // an even count (two wave rows); M above 128 is split over blockIdx.z
+  const int mfr = (M + 15) / 16;
+  const int nsplit = (mfr + 7) / 8;
+  const int mc = ((mfr + nsplit - 1) / nsplit + 1) / 2 * 2;
+  const int Mp = nsplit * mc * 16;
+  const int Kp = (K + CIK - 1) / CIK * CIK;
+  const float* bias_ptr = bias_ptr_f32(bias, x);
+  if (bias_ptr) TORCH_CHECK(bias->numel() == M, "conv2d_s1: bias size");
+  auto wp = at::empty({ks * ks, Mp, Kp}, w.options());
+  auto y = at::empty({B, M, H, W}, x.options());
+  const int valign = W % 8 == 0 && (uintptr_t)x.data_ptr() % 16 == 0 &&
+                     (uintptr_t)y.data_ptr() % 16 == 0;
+  const int ntx = (W + TW - 1) / TW, nty = (H + C_TH - 1) / C_TH;
+  dim3 grid(ntx * nty, B, nsplit);
+  auto stream = at::hip::getCurrentHIPStream();
+  const long long npack = (long long)ks * ks * Mp * Kp;
+  hipLaunchKernelGGL(conv2d_pack_w_kernel, dim3(esr_grid(npack)),
+                     dim3(ESR_BLOCK), 0, stream, npack,
+                     (const ushort*)w.data_ptr(), (ushort*)wp.data_ptr(),
+                     O, I, ks, Mp, Kp, (int)dgrad);
+  DISPATCH_ELEM(x.scalar_type(), [&] {
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream,
+                         (const ushort*)x.data_ptr(),
+                         (const ushort*)wp.data_ptr(), bias_ptr,
+                         (ushort*)y.data_ptr(), K, H, W, M, Kp, Mp, ntx,
+                         (int)act, valign);
+    };
+    auto by_mc = [&](auto ks_tag) {
+      constexpr int kKS = decltype(ks_tag)::value;
+      switch (mc) {
+        case 2: launch(conv2d_s1_core_kernel<elem_t, kKS, 2>); break;
+        case 4: launch(conv2d_s1_core_kernel<elem_t, kKS, 4>); break;
+        case 6: launch(conv2d_s1_core_kernel<elem_t, kKS, 6>); break;
+        default: launch(conv2d_s1_core_kernel<elem_t, kKS, 8>); break;
+      }
+    };
+    if (ks == 3) by_mc(std::integral_constant<int, 3>{});
+    else by_mc(std::integral_constant<int, 1>{});
+    return 0;
+  });
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return y;
+}
+
 // x [B,Cin,H,W] bf16|fp16, w [Cout,Cin,ks,ks] same dtype (unpacked),
 // bias fp32 | none
 at::Tensor conv2d_fwd_valu(const at::Tensor& x, const at::Tensor& w,
@@ -1131,6 +1493,80 @@ at::Tensor conv2d_dgrad_s2(const at::Tensor& dy, const at::Tensor& w,
   return dx;
 }
 
+// stage 1 of the stride-1 weight grad: per-block partial tiles
+// [ng][ciblks][coblks][32ci][64co][ntap] fp32
+static at::Tensor wgrad_s1_stage1(const at::Tensor& x, const at::Tensor& dpre,
+                                  int ks, int Cin_p, int Cout_p, int* ng_out) {
+  const int B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  const int Cout = dpre.size(1);
+  const int uw = (W + TW - 1) / TW;
+  const int ciblks = (Cin_p + 31) / 32, coblks = (Cout_p + 63) / 64;
+  // frames-per-block: accumulate several frames in registers before the
+  // flush (partial traffic / fpb) while keeping the grid >= ~1024
+  long long nb = (long long)B * uw * ciblks * coblks;
+  int fpb = 1;
+  while (fpb < 32 && fpb * 2 <= B && nb / (fpb * 2) >= 1024) fpb *= 2;
+  static const int abl = [] {
+    const char* e = getenv("ESR_WGRAD_ABL");
+    return e ? atoi(e) : 0;
+  }();
+  const int bblks = (B + fpb - 1) / fpb;
+  const int ng = bblks * uw;
+  const int ntap = ks * ks;
+  dim3 grid((unsigned)ng, ciblks, coblks);
+  auto part = at::empty({(long long)ng * ciblks * coblks * 32 * 64 * ntap},
+                        x.options().dtype(at::kFloat));
+  auto stream = at::hip::getCurrentHIPStream();
+  if (ks == 3)
+    hipLaunchKernelGGL((conv2d_wgrad_s1_kernel<3>), grid, dim3(256), 0,
+                       stream, (const ushort*)x.data_ptr(),
+                       (const ushort*)dpre.data_ptr(),
+                       part.data_ptr<float>(),
+                       Cin, H, W, Cout, Cin_p, Cout_p, uw, B, fpb, abl);
+  else
+    hipLaunchKernelGGL((conv2d_wgrad_s1_kernel<1>), grid, dim3(256), 0,
+                       stream, (const ushort*)x.data_ptr(),
+                       (const ushort*)dpre.data_ptr(),
+                       part.data_ptr<float>(),
+                       Cin, H, W, Cout, Cin_p, Cout_p, uw, B, fpb, abl);
+  *ng_out = ng;
+  return part;
+}
+
+// Stride-1 weight grad, both stages: dW [Cout, Cin, ks, ks] bf16, each
+// element the fp32 sum of its partials (stage 2 adds them in block order)
+// rounded once.  No zero fill, no padded fp32 result, no permute or cast
+// afterwards: two launches.
+at::Tensor conv2d_wgrad_s1(const at::Tensor& x, const at::Tensor& dpre,
+                           int64_t ks) {
+  check_bf16_4d(x, "conv2d_wgrad_s1: x");
+  check_bf16_4d(dpre, "conv2d_wgrad_s1: dpre");
+  TORCH_CHECK(ks == 1 || ks == 3, "conv2d_wgrad_s1: 3x3 or 1x1 only");
+  TORCH_CHECK(x.size(0) == dpre.size(0) && x.size(2) == dpre.size(2) &&
+              x.size(3) == dpre.size(3), "conv2d_wgrad_s1: x / dpre shapes");
+  const int Cin = x.size(1), Cout = dpre.size(1);
+  const int Cin_p = (Cin + 15) / 16 * 16, Cout_p = (Cout + 15) / 16 * 16;
+  const int ciblks = (Cin_p + 31) / 32, coblks = (Cout_p + 63) / 64;
+  int ng = 0;
+  auto part = wgrad_s1_stage1(x, dpre, (int)ks, Cin_p, Cout_p, &ng);
+  auto dw = at::empty({Cout, Cin, ks, ks}, x.options());
+  // elements of one partial tile set
+  const long long n = (long long)ciblks * coblks * 32 * 64 * ks * ks;
+  auto stream = at::hip::getCurrentHIPStream();
+  if (ks == 3)
+    hipLaunchKernelGGL((conv2d_wgrad_reduce_out_kernel<9>),
+                       dim3(esr_grid(n)), dim3(ESR_BLOCK), 0, stream, n,
+                       part.data_ptr<float>(), ng, coblks, Cin, Cout,
+                       (ushort*)dw.data_ptr());
+  else
+    hipLaunchKernelGGL((conv2d_wgrad_reduce_out_kernel<1>),
+                       dim3(esr_grid(n)), dim3(ESR_BLOCK), 0, stream, n,
+                       part.data_ptr<float>(), ng, coblks, Cin, Cout,
+                       (ushort*)dw.data_ptr());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dw;
+}
+
 // returns padded fp32 dW [Cout_p, Cin_p, ks, ks]
 at::Tensor conv2d_wgrad_mfma(const at::Tensor& x, const at::Tensor& dpre,
                              int64_t ks, int64_t stride,
@@ -1148,35 +1584,10 @@ at::Tensor conv2d_wgrad_mfma(const at::Tensor& x, const at::Tensor& dpre,
   auto stream = at::hip::getCurrentHIPStream();
   if (stride == 1) {
     const int ciblks = (Cin_p + 31) / 32, coblks = (Cout_p + 63) / 64;
-    // frames-per-block: accumulate several frames in registers before the
-    // atomic flush (atomic traffic / fpb) while keeping the grid >= ~2048
-    long long nb = (long long)B * uw * ciblks * coblks;
-    int fpb = 1;
-    while (fpb < 32 && fpb * 2 <= B && nb / (fpb * 2) >= 1024) fpb *= 2;
-    static const int abl = [] {
-      const char* e = getenv("ESR_WGRAD_ABL");
-      return e ? atoi(e) : 0;
-    }();
-    const int bblks = (B + fpb - 1) / fpb;
-    const int ng = bblks * uw;
     const int ntap = (int)(ks * ks);
-    dim3 grid((unsigned)ng, ciblks, coblks);
-    auto part = at::empty({(long long)ng * ciblks * coblks * 32 * 64 * ntap},
-                          x.options().dtype(at::kFloat));
-    if (ks == 3)
-      hipLaunchKernelGGL((conv2d_wgrad_s1_kernel<3>), grid, dim3(256), 0,
-                         stream, (const ushort*)x.data_ptr(),
-                         (const ushort*)dpre.data_ptr(),
-                         part.data_ptr<float>(),
-                         Cin, H, W, Cout, (int)Cin_p, (int)Cout_p, uw, B,
-                         fpb, abl);
-    else
-      hipLaunchKernelGGL((conv2d_wgrad_s1_kernel<1>), grid, dim3(256), 0,
-                         stream, (const ushort*)x.data_ptr(),
-                         (const ushort*)dpre.data_ptr(),
-                         part.data_ptr<float>(),
-                         Cin, H, W, Cout, (int)Cin_p, (int)Cout_p, uw, B,
-                         fpb, abl);
+    int ng = 0;
+    auto part = wgrad_s1_stage1(x, dpre, (int)ks, (int)Cin_p, (int)Cout_p,
+                                &ng);
     const long long nred = (long long)Cin_p * Cout_p * ntap;
     if (ks == 3)
       hipLaunchKernelGGL((conv2d_wgrad_reduce_kernel<9>),

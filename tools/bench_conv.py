@@ -137,6 +137,97 @@ def wgrad_component(args):
         print(f"{label:34s} {tn:10.3f} {tt:10.3f} {tt / tn:6.2f}")
 
 
+# deep stride-1 shapes of the flagship that SHAPES does not list (frames as
+# the step calls them)
+DEEP_EXTRA = [
+    ("lstm/convblock 64->64 @32", 384, 64, 64, 32, 32, 3, 1, "relu"),
+    ("offset 128->64 @32", 192, 128, 64, 32, 32, 3, 1, "relu"),
+    ("dcn offset/mask 64->216 @32", 128, 64, 216, 32, 32, 3, 1, None),
+]
+
+
+def bwd_parts_component(args):
+    """Deep stride-1 class, bf16: the whole backward of one conv as
+    _NativeConv2dFn.backward runs it (act grad + bias grad + dx + dW) under
+    ESR_CONV_BWD = auto (the default routing) / dgrad (input grad native,
+    weight grad aten) / native / aten, then input grad and weight grad
+    alone, native against aten with only that output asked for (aten's time
+    includes its layout transposes), and the forward on the 8x32-tile core
+    against conv2d_fwd_mfma.  Times in ms."""
+    import os
+    from esr_amd.ops.conv import ACT_IDS, _NativeConv2dFn, _pack
+    from esr_amd.ops.native import require_ext
+    ext = require_ext()
+    dev = "cuda:0"
+    bf = torch.bfloat16
+    torch.manual_seed(0)
+    deep = [sh for sh in SHAPES + DEEP_EXTRA
+            if sh[7] == 1 and sh[2] >= 32 and sh[3] >= 32]
+    print(f"{'shape':30s} {'B':>4s} | {'bwd auto':>8s} {'dgrad':>7s} "
+          f"{'native':>7s} {'aten':>7s} | {'dx core':>7s} {'dx old':>7s} {'dx aten':>7s} | "
+          f"{'dW nat':>7s} {'dW aten':>7s} | {'fwd core':>8s} {'fwd old':>7s}")
+    tot = [0.0] * 11
+    for label, B, cin, cout, h, w_, ks, stride, act in deep:
+        x = torch.randn(B, cin, h, w_, device=dev).to(bf)
+        wt = (torch.randn(cout, cin, ks, ks, device=dev) * 0.2).to(bf)
+        b = torch.randn(cout, device=dev).to(bf)
+        bias_f = b.float()
+        aid = ACT_IDS[act]
+        xg = x.clone().requires_grad_(True)
+        wg = wt.clone().requires_grad_(True)
+        bg = b.clone().requires_grad_(True)
+        y = _NativeConv2dFn.apply(xg, wg, bg, stride, aid)
+        gy = torch.randn_like(y)
+        dpre = ext.act_grad(gy, y.detach(), aid) if aid else gy
+        pad = [ks // 2, ks // 2]
+
+        def whole():
+            return torch.autograd.grad(y, (xg, wg, bg), gy, retain_graph=True)
+
+        def aten_part(mask):
+            return lambda: torch.ops.aten.convolution_backward(
+                dpre, x, wt, None, [1, 1], pad, [1, 1], False, [0, 0], 1,
+                mask)
+
+        def dx_old():
+            t = wt.transpose(0, 1)
+            if ks == 3:
+                t = t.flip((2, 3))
+            return ext.conv2d_fwd_mfma(dpre, _pack(t), None, cin, ks, 1, 0)
+
+        times = []
+        for mode in ("auto", "dgrad", "native", "aten"):
+            os.environ["ESR_CONV_BWD"] = mode
+            times.append(bench(whole, args.iters))
+        os.environ.pop("ESR_CONV_BWD")
+        times.append(bench(
+            lambda: ext.conv2d_s1(dpre, wt, None, 0, True), args.iters))
+        times.append(bench(dx_old, args.iters))
+        times.append(bench(aten_part([True, False, False]), args.iters))
+        times.append(bench(
+            lambda: ext.conv2d_wgrad_s1(x, dpre, ks), args.iters))
+        times.append(bench(aten_part([False, True, False]), args.iters))
+        times.append(bench(
+            lambda: ext.conv2d_s1(x, wt, bias_f, aid, False), args.iters))
+        times.append(bench(
+            lambda: ext.conv2d_fwd_mfma(x, _pack(wt), bias_f, cout, ks, 1,
+                                        aid), args.iters))
+        # the two forward kernels add in the same order: compare bits
+        same = torch.equal(ext.conv2d_s1(x, wt, bias_f, aid, False),
+                           ext.conv2d_fwd_mfma(x, _pack(wt), bias_f, cout,
+                                               ks, 1, aid))
+        tot = [a + t for a, t in zip(tot, times)]
+        t = times
+        print(f"{label:30s} {B:4d} | {t[0]:8.3f} {t[1]:7.3f} {t[2]:7.3f} "
+              f"{t[3]:7.3f} | {t[4]:7.3f} {t[5]:7.3f} {t[6]:7.3f} | "
+              f"{t[7]:7.3f} {t[8]:7.3f} | {t[9]:8.3f} {t[10]:7.3f}"
+              f"{'' if same else '  fwd bits differ'}", flush=True)
+    t = tot
+    print(f"{'TOTAL':30s} {'':4s} | {t[0]:8.3f} {t[1]:7.3f} {t[2]:7.3f} "
+          f"{t[3]:7.3f} | {t[4]:7.3f} {t[5]:7.3f} {t[6]:7.3f} | {t[7]:7.3f} "
+          f"{t[8]:7.3f} | {t[9]:8.3f} {t[10]:7.3f}")
+
+
 HBM_PEAK_TBS = 8.0   # MI355X HBM3E peak
 
 
@@ -200,6 +291,10 @@ def main():
     ap.add_argument("--bias-grad", action="store_true",
                     help="time act_grad + sum((0,2,3)) against "
                          "act_grad_bias / bias_grad, with achieved bytes/s")
+    ap.add_argument("--bwd-parts", action="store_true",
+                    help="deep stride-1 class: whole backward per conv under "
+                         "ESR_CONV_BWD=auto/native/aten, dx and dW alone "
+                         "against aten, forward core against the older kernel")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="bf16",
                     help="operand dtype of the native kernels and of the "
                          "MIOpen comparison (--wgrad stays bf16)")
@@ -211,6 +306,8 @@ def main():
         return valu2_component(args)
     if args.bias_grad:
         return bias_grad_component(args)
+    if args.bwd_parts:
+        return bwd_parts_component(args)
 
     from esr_amd.ops.conv import ACT_IDS, _NativeConv2dFn
     dev = "cuda:0"
