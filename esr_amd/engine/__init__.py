@@ -6,4 +6,5 @@ from .device_inference import infer_sequence_device  # noqa: F401
 from .streaming import StreamingESR  # noqa: F401
 from .multistream import MultiStreamESR  # noqa: F401
 from .graph_runner import GraphedBPTTStep, flatten_grads  # noqa: F401
-from .superresolve import super_resolve_store  # noqa: F401
+from .superresolve import (super_resolve_store,  # noqa: F401
+                           super_resolve_stores)

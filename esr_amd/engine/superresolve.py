@@ -24,6 +24,11 @@ back on the recording's own float64 clock and writes them as an EVS store.
 
 The first `mid` and last `seqn-1-mid` windows get no prediction and are not
 emitted (no edge padding); the summary reports the covered time span.
+
+`super_resolve_stores` converts a list of recordings with several of them in
+flight: each occupies a lane (a batch row) of one tick, and `sr_emit_lanes`
+appends every lane's rows to that lane's own chunk.  Its output per recording
+is `super_resolve_store`'s, byte for byte.
 """
 
 from __future__ import annotations
@@ -32,6 +37,7 @@ import logging
 import time
 import warnings
 from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -41,7 +47,7 @@ from ..data.store import GROUP_LEVELS, EventStore, EventStoreWriter
 from ..ops.native import get_ext
 from .capture import amp_autocast, capture_graph, state_holder
 
-__all__ = ["super_resolve_store", "tile_windows", "emit_window_torch",
+__all__ = ["super_resolve_store", "super_resolve_stores", "tile_windows", "emit_window_torch",
            "hash_phase_torch", "cell_counts_torch", "PHASE_Q"]
 
 log = logging.getLogger(__name__)
@@ -451,3 +457,400 @@ def super_resolve_store(model, src, dst, *, group, scale, seqn=3, window=2048,
             "windows": list(range(first_window, first_window + n_steps)),
             "stats": dev_stats}
     return summary
+
+
+# ---------------------------------------------------------------------------
+# several recordings at once: lanes of one batched tick
+
+def _open_recording(src, dst, *, group, scale, seqn, window, mode, capacity,
+                    max_windows):
+    """Open and tile one source the way `super_resolve_store` does, without
+    writing anything; raises ValueError naming the file."""
+    store = EventStore(src)
+    if group not in store.groups:
+        raise ValueError(f"{src}: no group {group!r} (has "
+                         f"{sorted(store.groups)})")
+    level = GROUP_LEVELS.get(group, 1)
+    H, W = store.sensor_resolution
+    lrH, lrW = round(H / level), round(W / level)
+    if lrH * scale > _MAX_DIM or lrW * scale > _MAX_DIM:
+        raise ValueError(f"{src}: HR grid {lrH * scale}x{lrW * scale} exceeds "
+                         f"{_MAX_DIM} pixels, the 15-bit coordinate of a "
+                         f"packed event")
+    n_src = store.num_events(group)
+    src_ts = np.asarray(store.ts(group)[:n_src], dtype=np.float64) if n_src \
+        else np.zeros(0)
+    tiles = tile_windows(src_ts, mode, window)
+    n_tiled = int(tiles["begin"].shape[0])
+    n_win = n_tiled if max_windows is None else min(n_tiled, int(max_windows))
+    if n_win < seqn:
+        raise ValueError(f"{src} [{group}]: {n_win} windows, fewer than "
+                         f"seqn = {seqn}")
+    if n_src > 2 ** 31 - 1:
+        raise ValueError(f"{src}: {n_src} events exceed the int32 row index "
+                         f"of the job table")
+    mid = (seqn - 1) // 2
+    n_steps = n_win - seqn + 1
+    begin, end = tiles["begin"][:n_win], tiles["end"][:n_win]
+    longest = int((end - begin).max())
+    if capacity is None:
+        capacity = max(1024, 4 * scale * scale * longest)
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError(f"capacity must be positive, got {capacity}")
+    jobs_np = np.zeros((n_steps, seqn, 4), dtype=np.int64)
+    for l in range(seqn):
+        jobs_np[:, l, 0] = begin[l:l + n_steps]
+        jobs_np[:, l, 1] = end[l:l + n_steps]
+    win_np = np.ascontiguousarray(np.stack(
+        [tiles["t0"][mid:mid + n_steps], tiles["t1"][mid:mid + n_steps]],
+        axis=1))
+    return SimpleNamespace(
+        src=src, dst=dst, store=store, lr=(lrH, lrW), n_src=n_src,
+        n_tiled=n_tiled, n_win=n_win, n_steps=n_steps, longest=longest,
+        capacity=capacity, jobs_np=jobs_np, win_np=win_np,
+        tail_events=int(tiles["tail_events"]),
+        events_in=int(end[n_win - 1] - begin[0]))
+
+
+@torch.no_grad()
+def super_resolve_stores(model, pairs, *, lanes, group, scale, seqn=3,
+                         window=2048, mode="events", redistribute="linear",
+                         seed=0, capacity=None, cell_cap=1023,
+                         chunk_windows=256, device="cuda:0", use_graphs=True,
+                         amp_dtype=None, max_windows=None, keep=False,
+                         checkpoint=None, max_bytes=8 << 30):
+    """`super_resolve_store` for a list of `(src, dst)` pairs with up to
+    `lanes` recordings in flight: lane s is row s of a batch-`lanes` tick
+    (fetch, splat, forward, `sr_emit_lanes`), on CUDA one control-block
+    upload and one graph replay.  A lane whose recording ends is handed to
+    the next recording of the list; recordings start in list order.  Every
+    `dst` and its summary (minus `seconds`) are what `super_resolve_store`
+    with the same arguments writes for that pair alone, given a model whose
+    result for one sample does not depend on the rest of the batch.
+
+    All sources must share one LR resolution; the recurrent state's dim 0
+    must be a multiple m of the lane count, lane s owning rows s, lanes + s,
+    ..., (m-1)*lanes + s.  The packed events of `lanes` recordings stay on
+    the device, at most `max_bytes`.  Returns `{dst: summary}`, with `keep`
+    `{dst: (summary, kept)}` as `super_resolve_store` returns them."""
+    if redistribute not in _MODES:
+        raise ValueError(f"redistribute must be one of {list(_MODES)}, got "
+                         f"{redistribute!r}")
+    if int(scale) != scale or int(scale) < 1:
+        raise ValueError(f"scale must be a positive integer, got {scale!r}")
+    scale, seqn = int(scale), int(seqn)
+    chunk_windows, lanes = int(chunk_windows), int(lanes)
+    if seqn < 1 or chunk_windows < 1 or int(cell_cap) < 1 \
+            or int(cell_cap) > 65535:
+        raise ValueError("seqn and chunk_windows must be positive and "
+                         "cell_cap must lie in [1, 65535]")
+    if lanes < 1:
+        raise ValueError(f"lanes must be positive, got {lanes}")
+    cell_cap = int(cell_cap)
+    device = torch.device(device)
+    on_gpu = device.type == "cuda"
+    pairs = [(str(src), str(dst)) for src, dst in pairs]
+    if not pairs:
+        return {}
+
+    # every source is opened and tiled before anything is written
+    recs = [_open_recording(src, dst, group=group, scale=scale, seqn=seqn,
+                            window=window, mode=mode, capacity=capacity,
+                            max_windows=max_windows) for src, dst in pairs]
+    lrH, lrW = recs[0].lr
+    for r in recs[1:]:
+        if r.lr != (lrH, lrW):
+            raise ValueError(
+                f"{r.src} [{group}]: LR resolution {r.lr[0]}x{r.lr[1]} "
+                f"differs from {lrH}x{lrW} of {recs[0].src}")
+    kH, kW = lrH * scale, lrW * scale
+    L = min(lanes, len(recs))
+    slot = max(max(r.n_src for r in recs), 1)
+    if L * slot * 4 > max_bytes or L * slot > 2 ** 31 - 1:
+        raise ValueError(
+            f"the event arena of {L} lanes x {slot} events takes "
+            f"{L * slot * 4} bytes; at most max_bytes = {max_bytes} bytes "
+            f"and {2 ** 31 - 1} events fit")
+    max_steps = max(r.n_steps for r in recs)
+    capacity_max = max(r.capacity for r in recs)
+    longest_max = max(r.longest for r in recs)
+    mid = (seqn - 1) // 2
+    rmode = _MODES[redistribute]
+    out_group = _output_group(group, scale)
+
+    ext = None
+    if on_gpu:
+        ext = get_ext()
+        if ext is None or not hasattr(ext, "sr_emit_lanes"):
+            ext = None
+            warnings.warn(
+                "super_resolve_stores: the native sr_emit_lanes kernel is not "
+                "built (run `python -m esr_amd.ops.native.build`); using the "
+                "torch forms", RuntimeWarning, stacklevel=2)
+
+    # static buffers: the graph's addresses never change
+    arena = torch.zeros(L * slot, dtype=torch.int32, device=device)
+    jobs_tab = torch.zeros(L * max_steps, seqn * 4, dtype=torch.int32,
+                           device=device)
+    wins_tab = torch.zeros(L * max_steps, 2, dtype=torch.float64,
+                           device=device)
+    lane_base = torch.arange(L, device=device) * max_steps
+    hr_out = torch.zeros(L * seqn, 2, kH, kW, device=device)
+    inp = hr_out.view(L, seqn, 2, kH, kW)
+    job = torch.zeros(L, seqn * 4, dtype=torch.int32, device=device)
+    win = torch.zeros(L, 2, dtype=torch.float64, device=device)
+    # control block, one upload per tick: lane_ctl [L, 2] = {active,
+    # capacity_s} as sr_emit_lanes reads it, then reset [L] and step [L]
+    ctl = torch.zeros(4 * L, dtype=torch.int64, device=device)
+    lane_ctl = ctl[:2 * L].view(L, 2)
+    reset_c, step_c = ctl[2 * L:3 * L], ctl[3 * L:]
+
+    model = model.to(device).eval()
+    if hasattr(model, "reset_states"):
+        model.reset_states()
+
+    def forward():
+        with amp_autocast(amp_dtype, device, cache_enabled=False):
+            return model(inp).float()
+
+    holder = state_holder(model)
+    state = None
+    probe = forward()
+    if holder is not None:
+        st = holder.state
+        model.reset_states()
+        if isinstance(st, (tuple, list)):
+            raise NotImplementedError(
+                "super_resolve_stores keeps the recurrence in one static "
+                "tensor; a tuple state (ConvLSTM) is not supported")
+        if isinstance(st, torch.Tensor):
+            if st.dim() < 1 or st.size(0) % L:
+                raise ValueError(
+                    f"the recurrent state {tuple(st.shape)} has no whole "
+                    f"number of rows per lane ({L} lanes)")
+            state = torch.zeros_like(st)
+    if tuple(probe.shape) != (L, 2, kH, kW):
+        raise ValueError(f"the model maps [{L}, {seqn}, 2, {kH}, {kW}] to "
+                         f"{tuple(probe.shape)}, not to [{L}, 2, {kH}, {kW}]")
+    del probe
+    rows_per_lane = state.size(0) // L if state is not None else 0
+
+    def lane_rows(flags):
+        """[L] lane flags -> a mask over the state's rows s, L+s, ..."""
+        return (flags != 0).repeat(rows_per_lane).view(
+            -1, *([1] * (state.dim() - 1)))
+
+    def predict():
+        # this tick's job rows and (t0, t1) of every lane, by step index
+        idx = lane_base + step_c.clamp(0, max_steps - 1)
+        torch.index_select(jobs_tab, 0, idx, out=job)
+        torch.index_select(wins_tab, 0, idx, out=win)
+        job.mul_(lane_ctl[:, :1] != 0)        # an idle lane's jobs are empty
+        hr_out.zero_()
+        if ext is not None:
+            ext.evs_batch_splat(arena, job.view(L * seqn, 4), hr_out, lrH,
+                                lrW, longest_max)
+        else:
+            batch_splat_torch(arena, job.view(L * seqn, 4), hr_out, lrH, lrW)
+        if state is not None:
+            state.masked_fill_(lane_rows(reset_c), 0)
+            holder.state = state
+        pred = forward()
+        if state is not None:
+            new = holder.state.to(state.dtype)
+            state.copy_(torch.where(lane_rows(lane_ctl[:, 0]), new, state))
+            holder.state = state
+        return pred.contiguous()
+
+    # per-lane emission state
+    if ext is not None:
+        rows = chunk_windows * capacity_max
+        cols = [torch.zeros(L, rows, dtype=dt, device=device)
+                for dt in (torch.uint16, torch.uint16, torch.float64,
+                           torch.int8)]
+        cs = torch.zeros(L, 5, dtype=torch.int64, device=device)
+        cs0 = torch.tensor([0, 0, 0, 0, mid], dtype=torch.int64,
+                           device=device)
+        zero_cursor = torch.zeros(1, dtype=torch.int64, device=device)
+        # row max_steps of every lane takes the writes of idle lanes
+        stats = torch.zeros(L * (max_steps + 1), 3, dtype=torch.int64,
+                            device=device)
+        stats_base = torch.arange(L, device=device) * (max_steps + 1)
+        scratch = ext.sr_emit_lanes_scratch(hr_out, L, 2 * kH * kW,
+                                            capacity_max)
+        stage = [{"block": torch.zeros(4 * L, dtype=torch.int64,
+                                       pin_memory=True), "done": None}
+                 for _ in range(2)]
+
+        def body():
+            pred = predict()
+            ext.sr_emit_lanes(pred, win, cols, cs, lane_ctl, capacity_max,
+                              cell_cap, rmode, int(seed), scratch)
+            row = torch.where(lane_ctl[:, 0] != 0,
+                              step_c.clamp(0, max_steps - 1),
+                              torch.full_like(step_c, max_steps))
+            stats.index_copy_(0, stats_base + row, cs[:, 1:4])
+            return pred
+
+        graph = None
+        if use_graphs:
+            # with an all-zero control block every lane is idle: the warm-up
+            # runs splat, commit and emit nothing
+            ctl.zero_()
+            graph, pred_out = capture_graph(body, warmup=2, device=device)
+
+    lane = [None] * L
+    queue = iter(recs)
+    results = {}
+    ticks = 0
+
+    def start(s):
+        """Hand lane s to the next recording of the list, if any."""
+        rec = next(queue, None)
+        if rec is None:
+            lane[s] = None
+            return
+        st = rec.store
+        packed = pack_events(
+            st._arr(f"{group}_xs")[:rec.n_src],
+            st._arr(f"{group}_ys")[:rec.n_src],
+            st._arr(f"{group}_ps")[:rec.n_src], name=f"{rec.src} [{group}]")
+        arena[s * slot:s * slot + rec.n_src].copy_(
+            torch.from_numpy(packed.copy()))
+        jobs_np = rec.jobs_np.copy()
+        jobs_np[:, :, :2] += s * slot         # row indices into the arena
+        lo = s * max_steps
+        jobs_tab[lo:lo + rec.n_steps].copy_(torch.from_numpy(
+            jobs_np.astype(np.int32).reshape(rec.n_steps, seqn * 4)))
+        wins_tab[lo:lo + rec.n_steps].copy_(torch.from_numpy(rec.win_np))
+        if ext is not None:
+            cs[s].copy_(cs0)                  # cursor 0, window index mid
+        writer = EventStoreWriter(rec.dst, (kH, kW))
+        lane[s] = SimpleNamespace(
+            rec=rec, step=0, gathered=0, reset=True, writer=writer,
+            appender=writer.open_group(out_group), pending=[],
+            stats_np=np.zeros((rec.n_steps, 3), dtype=np.int64),
+            kept={"pred": [], "counts": []}, t_start=time.perf_counter())
+
+    def drain(s):
+        ln = lane[s]
+        if ext is not None:
+            n = int(cs[s, 0].item())          # the drain's one synchronisation
+            if not 0 <= n <= rows:
+                raise RuntimeError(f"append cursor {n} of lane {s} outside "
+                                   f"the chunk of {rows} rows")
+            ln.appender.append(*(c[s, :n].cpu().numpy() for c in cols))
+            cs[s, :1].copy_(zero_cursor)
+        else:
+            ln.appender.append(*(np.concatenate([e[f] for e in ln.pending])
+                                 for f in ("xs", "ys", "ts", "ps")))
+            ln.pending = []
+        ln.gathered = 0
+
+    def finish(s):
+        ln, rec = lane[s], lane[s].rec
+        ln.appender.close()
+        if ext is not None:
+            lo = s * (max_steps + 1)
+            ln.stats_np = stats[lo:lo + rec.n_steps].cpu().numpy()
+        stats_np = ln.stats_np
+        overflowed = np.nonzero(stats_np[:, 2] > 0)[0] + mid
+        dropped = int(stats_np[:, 2].sum())
+        if overflowed.size:
+            log.warning(
+                "super_resolve_stores: %d of %d windows overflowed capacity "
+                "%d; %d events dropped (%s)", overflowed.size, rec.n_steps,
+                rec.capacity, dropped, rec.dst)
+        summary = {
+            "source": rec.src, "group": group, "output_group": out_group,
+            "checkpoint": None if checkpoint is None else str(checkpoint),
+            "scale": scale, "seqn": seqn,
+            "window": int(window) if mode == "events" else float(window),
+            "mode": mode, "redistribute": redistribute, "seed": int(seed),
+            "capacity": rec.capacity, "cell_cap": cell_cap,
+            "windows_tiled": rec.n_tiled, "windows_emitted": rec.n_steps,
+            "windows_skipped_edges": rec.n_win - rec.n_steps,
+            "tail_events_dropped": rec.tail_events,
+            "events_in": rec.events_in,
+            "events_out": int(stats_np[:, 1].sum()),
+            "events_dropped": dropped,
+            "windows_overflowed": int(overflowed.size),
+            "overflowed_windows": [int(w) for w in overflowed[:100]],
+            "covered": [float(rec.win_np[0, 0]), float(rec.win_np[-1, 1])],
+        }
+        ln.writer.meta["sr"] = dict(summary)
+        ln.writer.close()
+        summary["seconds"] = time.perf_counter() - ln.t_start
+        if keep:
+            results[rec.dst] = (summary, {
+                "pred": torch.stack(ln.kept["pred"]),
+                "counts": torch.stack(ln.kept["counts"]),
+                "windows": list(range(mid, mid + rec.n_steps)),
+                "stats": torch.from_numpy(stats_np)})
+        else:
+            results[rec.dst] = summary
+
+    try:
+        for s in range(L):
+            start(s)
+        while any(ln is not None for ln in lane):
+            block = [0] * (4 * L)
+            for s, ln in enumerate(lane):
+                if ln is not None:
+                    block[2 * s], block[2 * s + 1] = 1, ln.rec.capacity
+                    block[2 * L + s] = int(ln.reset)
+                    block[3 * L + s] = ln.step
+                    ln.reset = False
+            if ext is not None:
+                # double-buffered pinned staging: a block is rewritten only
+                # after the copy that read it two ticks ago has finished
+                stg = stage[ticks % 2]
+                if stg["done"] is not None:
+                    stg["done"].synchronize()
+                stg["block"].copy_(torch.tensor(block, dtype=torch.int64))
+                ctl.copy_(stg["block"], non_blocking=True)
+                stg["done"] = torch.cuda.Event()
+                stg["done"].record(torch.cuda.current_stream(device))
+                if graph is not None:
+                    graph.replay()
+                    pred = pred_out
+                else:
+                    pred = body()
+            else:
+                ctl.copy_(torch.tensor(block, dtype=torch.int64))
+                pred = predict()
+            ticks += 1
+            for s, ln in enumerate(lane):
+                if ln is None:
+                    continue
+                rec = ln.rec
+                if ext is None:
+                    ev = emit_window_torch(
+                        pred[s], float(rec.win_np[ln.step, 0]),
+                        float(rec.win_np[ln.step, 1]), capacity=rec.capacity,
+                        cell_cap=cell_cap, mode=redistribute, seed=seed,
+                        window_index=mid + ln.step)
+                    ln.stats_np[ln.step] = (ev["total"], ev["emitted"],
+                                            ev["dropped"])
+                    ln.pending.append(ev)
+                if keep:
+                    ln.kept["pred"].append(pred[s].clone())
+                    ln.kept["counts"].append(
+                        ev["counts"].clone() if ext is None else
+                        scratch[0].view(L, 2, kH, kW)[s].long().clone())
+                ln.step += 1
+                ln.gathered += 1
+                ended = ln.step == rec.n_steps
+                if ln.gathered == chunk_windows or ended:
+                    drain(s)
+                if ended:
+                    finish(s)
+                    start(s)
+    finally:
+        for ln in lane:
+            if ln is not None:                # an error mid-run: close files
+                ln.appender.close()
+        if hasattr(model, "reset_states"):
+            model.reset_states()
+    return {rec.dst: results[rec.dst] for rec in recs}      # list order

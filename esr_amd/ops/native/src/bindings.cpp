@@ -108,6 +108,12 @@ void sr_emit_window(const at::Tensor&, const at::Tensor&,
                     const std::vector<at::Tensor>&, at::Tensor&, int64_t,
                     int64_t, int64_t, int64_t,
                     const std::vector<at::Tensor>&);
+std::vector<at::Tensor> sr_emit_lanes_scratch(const at::Tensor&, int64_t,
+                                              int64_t, int64_t);
+void sr_emit_lanes(const at::Tensor&, const at::Tensor&,
+                   const std::vector<at::Tensor>&, at::Tensor&,
+                   const at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                   const std::vector<at::Tensor>&);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
@@ -204,5 +210,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "append one predicted window [2,kH,kW] as sorted event rows to the "
         "typed chunk columns at a device cursor; int64 offsets, integer "
         "phases, float64 timestamps, overflow counted; capture-safe");
+  m.def("sr_emit_lanes_scratch", &sr_emit_lanes_scratch,
+        "scratch of sr_emit_lanes for (lanes, ncells, capacity_max), "
+        "allocated once");
+  m.def("sr_emit_lanes", &sr_emit_lanes,
+        "sr_emit_window for S maps [S,2,kH,kW] at once: per-lane clocks, "
+        "cursors, capacities and window indices, inactive lanes untouched; "
+        "one scan and one sort for all lanes; capture-safe");
   m.attr("gfx_arch") = "gfx950";
 }

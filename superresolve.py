@@ -11,8 +11,23 @@ import torch
 import yaml
 
 from esr_amd.data import read_datalist
+from esr_amd.data.store import GROUP_LEVELS, EventStore
 from esr_amd.engine import load_model_from_checkpoint
-from esr_amd.engine.superresolve import super_resolve_store
+from esr_amd.engine.superresolve import (super_resolve_store,
+                                         super_resolve_stores)
+
+
+def partition_by_resolution(pairs, group):
+    """Split (src, dst) pairs into lists of one LR resolution each, keeping
+    the list's order inside every part; `super_resolve_stores` runs one
+    resolution at a time."""
+    parts = {}
+    level = GROUP_LEVELS.get(group, 1)
+    for src, dst in pairs:
+        H, W = EventStore(src).sensor_resolution
+        parts.setdefault((round(H / level), round(W / level)),
+                         []).append((src, dst))
+    return list(parts.values())
 
 
 def main():
@@ -42,6 +57,10 @@ def main():
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--no_graphs", action="store_true")
     p.add_argument("--max_windows", type=int, default=None)
+    p.add_argument("--lanes", type=int, default=1,
+                   help="with --data_list: recordings in flight at once, as "
+                        "rows of one batched graph replay (default 1: one "
+                        "recording after the other)")
     args = p.parse_args()
 
     logging.basicConfig(level=logging.WARNING, stream=sys.stderr)
@@ -62,15 +81,26 @@ def main():
         pairs = [(src, out_root / f"{Path(src).stem}.evs")
                  for src in read_datalist(args.data_list)]
 
+    if args.lanes < 1:
+        raise SystemExit("--lanes must be positive")
+    kw = dict(group=args.group, scale=args.scale, seqn=args.seqn,
+              window=window, mode=args.mode, redistribute=args.redistribute,
+              seed=args.seed, capacity=args.capacity, cell_cap=args.cell_cap,
+              device=device, use_graphs=not args.no_graphs,
+              amp_dtype=amp_dtype, max_windows=args.max_windows,
+              checkpoint=args.model_path)
     summaries = {}
-    for src, dst in pairs:
-        summaries[str(dst)] = super_resolve_store(
-            model, src, str(dst), group=args.group, scale=args.scale,
-            seqn=args.seqn, window=window, mode=args.mode,
-            redistribute=args.redistribute, seed=args.seed,
-            capacity=args.capacity, cell_cap=args.cell_cap, device=device,
-            use_graphs=not args.no_graphs, amp_dtype=amp_dtype,
-            max_windows=args.max_windows, checkpoint=args.model_path)
+    if args.lanes > 1 and args.data_list is not None:
+        done = {}
+        for part in partition_by_resolution(pairs, args.group):
+            done.update(super_resolve_stores(
+                model, [(src, str(dst)) for src, dst in part],
+                lanes=args.lanes, **kw))
+        summaries = {str(dst): done[str(dst)] for _, dst in pairs}
+    else:
+        for src, dst in pairs:
+            summaries[str(dst)] = super_resolve_store(model, src, str(dst),
+                                                      **kw)
     out = next(iter(summaries.values())) if args.input is not None \
         else summaries
     print(yaml.safe_dump(out, sort_keys=False), end="")
