@@ -24,7 +24,8 @@ import torch.nn.functional as F
 
 from .store import EventStoreWriter
 
-__all__ = ["simulate_events", "sample_contrast_thresholds",
+__all__ = ["simulate_events", "simulate_events_log", "simulate_log_slab",
+           "check_timestamps", "sample_contrast_thresholds",
            "frames_to_event_store"]
 
 _LOG_EPS = 1e-3
@@ -38,17 +39,29 @@ def sample_contrast_thresholds(rng: np.random.Generator):
     return cp, cn
 
 
-def simulate_events(frames: np.ndarray, timestamps: np.ndarray,
-                    cp: float = 0.2, cn: float = 0.2,
-                    refractory: float = 0.0) -> np.ndarray:
-    """Simulate an event stream from a frame sequence.
+def check_timestamps(timestamps) -> np.ndarray:
+    """Timestamps as float64 [T]; ValueError unless they are finite and
+    strictly increasing.  -0.0 becomes +0.0, so no event time is -0.0."""
+    ts = np.asarray(timestamps, dtype=np.float64) + 0.0
+    if ts.ndim != 1:
+        raise ValueError("timestamps must be one-dimensional")
+    if not np.isfinite(ts).all():
+        raise ValueError("timestamps must be finite")
+    if ts.size > 1 and not (np.diff(ts) > 0).all():
+        raise ValueError("timestamps must be strictly increasing")
+    return ts
 
-    frames: [T, H, W] in [0, 1]; timestamps: [T] seconds (increasing).
-    Returns [4, N] float64 (x, y, t, p) sorted by t.
-    """
-    T, H, W = frames.shape
-    logf = np.log(frames.astype(np.float64) + _LOG_EPS)
-    ref = logf[0].copy()          # per-pixel reference level at last event
+
+def simulate_log_slab(logf, timestamps, cp, cn, refractory, ref, t_last):
+    """The intervals of one slab of log frames, from the per-pixel state
+    (`ref`, `t_last`: float64 [H, W]; `t_last` is -inf where the pixel has
+    no event yet and is only kept up when refractory > 0).  Returns
+    (events [4, N], ref, t_last); the state passed in is not modified.
+    `simulate_events_log` documents the model."""
+    T, H, W = logf.shape
+    use_ref = refractory > 0
+    if use_ref:
+        t_last = t_last.copy()
     xs_all, ys_all, ts_all, ps_all = [], [], [], []
 
     yy, xx = np.mgrid[0:H, 0:W]
@@ -68,25 +81,94 @@ def simulate_events(frames: np.ndarray, timestamps: np.ndarray,
                 # linear interpolation of the crossing time inside [t0, t1]
                 target = ref[m] + pol * C * i
                 denom = (l1 - l0)[m]
-                frac = np.where(np.abs(denom) > 1e-12,
-                                (target - l0[m]) / denom, 0.5)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    frac = np.where(np.abs(denom) > 1e-12,
+                                    (target - l0[m]) / denom, 0.5)
                 frac = np.clip(frac, 0.0, 1.0)
                 t = t0 + frac * (t1 - t0)
-                xs_all.append(xx[m])
-                ys_all.append(yy[m])
+                x, y = xx[m], yy[m]
+                if use_ref:
+                    # a pixel crosses in one direction per interval, so this
+                    # loop visits its crossings in the order they occur
+                    keep = (t - t_last[m]) >= refractory
+                    x, y, t = x[keep], y[keep], t[keep]
+                    t_last[y, x] = t
+                xs_all.append(x)
+                ys_all.append(y)
                 ts_all.append(t)
-                ps_all.append(np.full(m.sum(), pol))
+                ps_all.append(np.full(t.shape[0], pol))
         # update reference level to the last crossed threshold
         ref = ref + n_pos * cp - n_neg * cn
 
     if not ts_all:
-        return np.zeros((4, 0))
+        return np.zeros((4, 0)), ref, t_last
     xs = np.concatenate(xs_all).astype(np.float64)
     ys = np.concatenate(ys_all).astype(np.float64)
     ts = np.concatenate(ts_all)
     ps = np.concatenate(ps_all)
     order = np.argsort(ts, kind="stable")
-    return np.stack([xs[order], ys[order], ts[order], ps[order]])
+    return np.stack([xs[order], ys[order], ts[order], ps[order]]), ref, t_last
+
+
+def simulate_events_log(logf: np.ndarray, timestamps: np.ndarray,
+                        cp: float, cn: float,
+                        refractory: float = 0.0) -> np.ndarray:
+    """Simulate an event stream from log-intensity frames: the oracle of the
+    device simulator (data/simulate_device.py, ops/native/src/esim.hip).
+
+    logf: float64 [T, H, W], taken as given; timestamps: [T] seconds, finite
+    and strictly increasing.  Returns [4, N] float64 (x, y, t, p).
+
+    All arithmetic is float64 with every operation rounded once.  Per
+    interval k = 1..T-1 and pixel, with ref starting at logf[0]:
+
+        dl = l1 - ref
+        n_pos = floor(max(dl, 0) / cp),  n_neg = floor(max(-dl, 0) / cn)
+        crossing i = 1..n of polarity pol (C = cp or cn):
+            target = ref + (pol * C) * i
+            frac = |l1 - l0| > 1e-12 ? (target - l0) / (l1 - l0) : 0.5,
+                   clipped to [0, 1]
+            t = t0 + frac * (t1 - t0)
+        ref = (ref + n_pos * cp) - n_neg * cn
+
+    Refractory rule (applied when refractory > 0): per pixel, in the order
+    the crossings occur (k, then i), a crossing becomes an event iff the
+    pixel has no earlier event or t - t_last >= refractory; only an emitted
+    event moves t_last; ref advances whether or not the event is suppressed.
+
+    Order: sorted lexicographically by (t, k, polarity with + first, i, y,
+    x), which is what a stable sort by t of the crossings enumerated in
+    (k, polarity, i, y, x) order yields.
+    """
+    logf = np.asarray(logf, dtype=np.float64)
+    if logf.ndim != 3:
+        raise ValueError("logf must be [T, H, W]")
+    ts = check_timestamps(timestamps)
+    if ts.shape[0] != logf.shape[0]:
+        raise ValueError("one timestamp per frame is required")
+    if not (cp > 0 and cn > 0):
+        raise ValueError("contrast thresholds must be positive")
+    if not refractory >= 0:
+        raise ValueError("the refractory period must be >= 0")
+    if logf.shape[0] == 0:
+        return np.zeros((4, 0))
+    t_last = np.full(logf.shape[1:], -np.inf)
+    ev, _, _ = simulate_log_slab(logf, ts, cp, cn, refractory,
+                                 logf[0].copy(), t_last)
+    return ev
+
+
+def simulate_events(frames: np.ndarray, timestamps: np.ndarray,
+                    cp: float = 0.2, cn: float = 0.2,
+                    refractory: float = 0.0) -> np.ndarray:
+    """Simulate an event stream from a frame sequence.
+
+    frames: [T, H, W] in [0, 1]; timestamps: [T] seconds (increasing).
+    Returns [4, N] float64 (x, y, t, p) sorted by t: `simulate_events_log`
+    on log(frames + 1e-3).
+    """
+    logf = np.log(frames.astype(np.float64) + _LOG_EPS)
+    return simulate_events_log(logf, timestamps, cp, cn, refractory)
 
 
 def _scale_frames(frames: np.ndarray, level: int) -> np.ndarray:

@@ -21,7 +21,8 @@ work) plus a JSON metadata file:
 
 `EventStoreWriter.add_group` writes a group in one call;
 `EventStoreWriter.open_group` streams one piece by piece (.npy headers written
-last into a reserved region), for outputs that do not fit in host memory.
+last into a reserved region), for outputs that do not fit in host memory;
+`EventStoreWriter.open_images` does the same for the frames.
 
 Groups follow the reference's naming: 'ori', 'down2', 'down4', 'down8',
 'down16' (and 'down8_real' for real-sensor captures).
@@ -74,6 +75,12 @@ class EventStoreWriter:
                 np.asarray(timestamps, dtype=np.float64))
         self.meta["num_images"] = int(images.shape[0])
 
+    def open_images(self, shape) -> "ImageAppender":
+        """The frames of `add_images` written piece by piece (`append`, then
+        `close`): uint8 frames of `shape` = (H, W), so a long video is never
+        held at once.  The files read back exactly as `add_images`'s."""
+        return ImageAppender(self, shape)
+
     def close(self):
         with open(self.path / "meta.json", "w") as f:
             json.dump(self.meta, f)
@@ -88,14 +95,16 @@ class EventStoreWriter:
 _NPY_HEADER_BYTES = 128      # magic, version, length and a padded dict
 
 
-def _npy_header(dtype, n: int) -> bytes:
+def _npy_header(dtype, n: int, item_shape=()) -> bytes:
     """A version 1.0 .npy header of exactly _NPY_HEADER_BYTES bytes for a
-    1-D little-endian array of `n` items.  The format lets the dict be
-    padded with spaces before its closing newline, so the size does not
-    depend on `n` and the header can be written after the data."""
+    little-endian C-order array of `n` items of shape `item_shape` (1-D by
+    default).  The format lets the dict be padded with spaces before its
+    closing newline, so the size does not depend on `n` and the header can
+    be written after the data."""
     descr = np.lib.format.dtype_to_descr(np.dtype(dtype))
+    shape = "".join(f"{int(d)}, " for d in (n, *item_shape)).rstrip()
     text = (f"{{'descr': {descr!r}, 'fortran_order': False, "
-            f"'shape': ({int(n)},), }}").encode("latin1")
+            f"'shape': ({shape}), }}").encode("latin1")
     room = _NPY_HEADER_BYTES - 10
     if len(text) + 1 > room:
         raise ValueError("npy header does not fit its reserved region")
@@ -135,6 +144,49 @@ class GroupAppender:
             f.close()
         self._files = []
         self.writer.meta["groups"][self.prefix] = int(self.n)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class ImageAppender:
+    """Streams frames to images.npy and their timestamps to image_ts.npy in
+    `GroupAppender`'s manner: reserved header regions, written on `close`."""
+
+    def __init__(self, writer: "EventStoreWriter", shape):
+        self.writer = writer
+        self.shape = tuple(int(d) for d in shape)
+        self.n = 0
+        self._img = open(writer.path / "images.npy", "wb")
+        self._ts = open(writer.path / "image_ts.npy", "wb")
+        for f in (self._img, self._ts):
+            f.write(b"\x00" * _NPY_HEADER_BYTES)
+
+    def append(self, images, timestamps) -> None:
+        images = np.ascontiguousarray(np.asarray(images, dtype=np.uint8))
+        ts = np.ascontiguousarray(np.asarray(timestamps, dtype="<f8"))
+        if images.shape[1:] != self.shape or ts.shape != images.shape[:1]:
+            raise ValueError(
+                f"expected frames [n, {self.shape[0]}, {self.shape[1]}] and "
+                f"one timestamp each, got {images.shape} and {ts.shape}")
+        self._img.write(images.tobytes())
+        self._ts.write(ts.tobytes())
+        self.n += images.shape[0]
+
+    def close(self) -> None:
+        if self._img is None:
+            return
+        self._img.seek(0)
+        self._img.write(_npy_header(np.uint8, self.n, self.shape))
+        self._ts.seek(0)
+        self._ts.write(_npy_header(np.dtype("<f8"), self.n))
+        self._img.close()
+        self._ts.close()
+        self._img = self._ts = None
+        self.writer.meta["num_images"] = int(self.n)
 
     def __enter__(self):
         return self

@@ -22,7 +22,7 @@ SOURCES = [SRC / "bindings.cpp", SRC / "deform_conv.hip",
            SRC / "event_ops.hip", SRC / "conv2d.hip", SRC / "redistribute.hip",
            SRC / "flat_adam.hip", SRC / "stream_ingest.hip",
            SRC / "batch_splat.hip", SRC / "eval_metrics.hip",
-           SRC / "sr_emit.hip"]
+           SRC / "sr_emit.hip", SRC / "esim.hip"]
 
 
 def build(verbose: bool = False) -> str:

@@ -115,6 +115,21 @@ void sr_emit_lanes(const at::Tensor&, const at::Tensor&,
                    const at::Tensor&, int64_t, int64_t, int64_t, int64_t,
                    const std::vector<at::Tensor>&);
 
+// esim.hip
+std::vector<at::Tensor> esim_scratch(const at::Tensor&, int64_t, int64_t);
+void esim_count(const at::Tensor&, const at::Tensor&, const at::Tensor&,
+                const at::Tensor&, int64_t, int64_t, double, double, double,
+                const std::vector<at::Tensor>&, at::Tensor&);
+void esim_scan(int64_t, const std::vector<at::Tensor>&, at::Tensor&);
+std::vector<int64_t> esim_emit(const at::Tensor&, const at::Tensor&,
+                               at::Tensor&, at::Tensor&, int64_t, int64_t,
+                               double, double, double, int64_t,
+                               const std::vector<at::Tensor>&);
+void esim_sort(int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+               const std::vector<at::Tensor>&);
+void esim_unpack(int64_t, const std::vector<at::Tensor>&,
+                 const std::vector<at::Tensor>&);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deform_conv2d_forward", &deform_conv2d_forward,
         "modulated deformable conv forward (gfx950)");
@@ -217,5 +232,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sr_emit_window for S maps [S,2,kH,kW] at once: per-lane clocks, "
         "cursors, capacities and window indices, inactive lanes untouched; "
         "one scan and one sort for all lanes; capture-safe");
+  m.def("esim_scratch", &esim_scratch,
+        "scratch of the event simulator for (npix, capacity), allocated once");
+  m.def("esim_count", &esim_count,
+        "events per pixel over intervals k0+1..k0+nint of a float64 [S,H,W] "
+        "slab of log frames, state untouched; stats = {total, largest "
+        "crossing count, bad-input flag}");
+  m.def("esim_scan", &esim_scan,
+        "int64 exclusive sum of the simulator's counts and their total");
+  m.def("esim_emit", &esim_emit,
+        "the walk of esim_count, writing (tie-break key, t) per event and "
+        "committing ref and t_last; returns {pix_bits, i_bits, key_bits}");
+  m.def("esim_sort", &esim_sort,
+        "0: sort by the tie-break key on the bits in use and make the "
+        "pack_events words; 1: stable sort by the float64 timestamp");
+  m.def("esim_unpack", &esim_unpack,
+        "sorted (t, word) pairs -> uint16 x, uint16 y, float64 t, int8 p");
   m.attr("gfx_arch") = "gfx950";
 }

@@ -25,6 +25,10 @@ def main():
     p.add_argument("--frames", type=int, default=32, help="esim mode")
     p.add_argument("--mode", choices=["emitter", "esim"], default="emitter")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device", default=None,
+                   help="esim mode: simulate on this device (cuda:0 | cpu) "
+                        "through the slab-by-slab device pipeline; default: "
+                        "the numpy simulator")
     p.add_argument("--split", type=float, default=0.75,
                    help="train fraction; writes train/valid datalists")
     args = p.parse_args()
@@ -58,7 +62,14 @@ def main():
             frames = np.stack(frames)
             ts = np.linspace(0, 0.5, args.frames)
             pth = out / f"sim{i:03d}.evs"
-            frames_to_event_store(pth, frames, ts, seed=args.seed + i)
+            if args.device is None:
+                frames_to_event_store(pth, frames, ts, seed=args.seed + i)
+            else:
+                from esr_amd.data.simulate_device import \
+                    frames_to_event_store_device
+                frames_to_event_store_device(pth, frames, ts,
+                                             seed=args.seed + i,
+                                             device=args.device)
             paths.append(str(pth))
 
     n_train = max(int(len(paths) * args.split), 1)
